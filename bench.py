@@ -15,9 +15,15 @@ inside the timed region: SURVEY 8(d); `extra.step_pooled_state_us` is the step w
 The ConvGRU between lookup and BA is out of scope.
 N=1 workload = BASELINE.json configs[1] shape: 25 KF / 96 edges / 512x512 frames (64x64 maps).
 
-    python bench.py --gpus 1 --steps 50 --warmup 10
+    python bench.py --gpus 1 --steps 50 --warmup 10 [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W [--window 64_512]
+
+A plain run sets up, warms up, times the steps, writes the last timed step's outputs (--dump-outputs) and prints the line:
+`value`, `ms_per_step` and the roofline (whose lookup times come from the timed steps themselves).  --full adds everything
+else the line has carried: the untimed loops after the timed region (ba device time, the step without the state reset,
+under the other edge-tensor modes and without the lookup's timing events), the weak-scaling 1-GPU point, the untimed
+extras (--no-extras leaves them out) and the CPU baseline with the ATE figures (--no-cpu-baseline leaves it out).
 
 Rank 0 prints ONE JSON line.  For N > 1 the edge set is sharded by source frame over the ranks, the reduced camera
 system is all-reduced over RCCL once per Gauss-Newton iteration and the updated inverse depths of the frames a rank
@@ -102,7 +108,13 @@ def main():
                          "default: droid_backends.ba_clamped, the clamp in ba's last launch)")
     ap.add_argument("--backend", default=os.environ.get("DBA_BENCH_BACKEND", "nccl"), choices=["nccl", "gloo"],
                     help="process-group backend of the exchange step (gloo: host-staged, several ranks may share one GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beyond the headline: untimed loops, extras, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned (rank 0) as float32 DIR/<name>.npy")
     args = ap.parse_args()
+    if not args.full:
+        args.no_extras = args.no_cpu_baseline = True
 
     from dbaf_amd import synthetic as syn
     from dbaf_amd import projective_ops as pops
@@ -241,6 +253,7 @@ def main():
         e_.record()   # (creates the underlying hipEvent_t; the lookup's pair is re-recorded by the kernel dispatch itself)
     ev_step = [torch.cuda.Event(enable_timing=True) for _ in range(max(total, 32) + 1)]
     keep = [None] * ncopies  # the last outputs stay alive: the allocator hands out other lines for the next ones
+    last_out = {"step": total - 1}   # the last timed step's outputs, for --dump-outputs (emptied after the timed loop)
 
     K_b4 = K[0]
     no_lookup_events = os.environ.get("DBA_BENCH_NO_LOOKUP_EVENTS") == "1"   # (A/B: what the dispatch's two timing events cost a step)
@@ -270,19 +283,21 @@ def main():
         # stream (hipExtLaunchKernelGGL through dba_corr_lookup_arm_timing): the dispatch's own start / end timestamps;
         # event.record() around the call would put two marker packets (~5 us of idle each) into every step
         if lookup is not None:
-            coords1, _ = pops.projective_transform(poses[None], disps[None], K, ii_, jj_)
+            coords1, valid1 = pops.projective_transform(poses[None], disps[None], K, ii_, jj_)
             ev[4 * i].record()
             c = lookup(coords1)
             ev[4 * i + 1].record()
         elif n_loc == 0:
             c = None
         elif fused:     # reprojection in the lookup's prologue: one launch, the coordinates are written for the caller
-            c, coords1, _ = corr_of(i).lookup_reprojected(poses, disps, K_b4, ii_, jj_,
-                                                          timing=(ev[4 * i], ev[4 * i + 1]) if (lookup_events and not no_lookup_events) else None)
+            c, coords1, valid1 = corr_of(i).lookup_reprojected(poses, disps, K_b4, ii_, jj_,
+                                                               timing=(ev[4 * i], ev[4 * i + 1]) if (lookup_events and not no_lookup_events) else None)
         else:
-            coords1, _ = pops.projective_transform(poses[None], disps[None], K, ii_, jj_)
+            coords1, valid1 = pops.projective_transform(poses[None], disps[None], K, ii_, jj_)
             c = corr_of(i)(coords1, timing=(ev[4 * i], ev[4 * i + 1]))
         keep[i % ncopies] = c
+        if i == last_out.get("step") and c is not None:   # what the last timed step's caller receives
+            last_out.update(corr=c, coords=coords1, valid=valid1)
         if graph_mode != "none" and n_loc > 0:
             g = caller_graph_fused() if graph_mode == "gather" else caller_graph(m_bool if graph_mode == "bool" else None)
             if graph_mode != "same":
@@ -327,23 +342,30 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
 
+    last_out.pop("step")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"poses": poses, "disps": disps, **last_out})
+    last_out.clear()
+
     ks = range(args.warmup, total)
     look_us = np.array([ev[4 * i].elapsed_time(ev[4 * i + 1]) for i in ks]) * 1e3 if corrs and args.steps else np.zeros(1)
     # ba(itrs=2) device time for SURVEY 8(d)'s gn_iter GB/s: a short untimed loop (its two events stay out of the timed steps)
-    nb = min(10, total)
+    nb = min(10, total) if args.full else 0
     for i in range(nb):
         step(i, time_ba=True)
     torch.cuda.synchronize()
     # the step without the state reset (round 3's method: pristine copies out of a pool filled outside the timed region)
-    refill_pool()
-    torch.cuda.synchronize()
-    tp = time.perf_counter()
-    for i in range(args.warmup, total):
-        step(i, pooled=True)
-    torch.cuda.synchronize()
-    pooled_us = (time.perf_counter() - tp) / max(args.steps, 1) * 1e6
+    pooled_us = None
+    if args.full:
+        refill_pool()
+        torch.cuda.synchronize()
+        tp = time.perf_counter()
+        for i in range(args.warmup, total):
+            step(i, pooled=True)
+        torch.cuda.synchronize()
+        pooled_us = (time.perf_counter() - tp) / max(args.steps, 1) * 1e6
     mode_us = {}
-    if shard is None and n_loc > 0:
+    if args.full and shard is None and n_loc > 0:
         for gm in ("same", "none", "fresh", "bool", "gather"):
             for i in range(min(args.warmup, 3)):
                 step(i, graph_mode=gm)
@@ -355,7 +377,7 @@ def main():
             mode_us[gm] = (time.perf_counter() - tp) / max(args.steps, 1) * 1e6
     # what the roofline's own instrumentation costs the timed step: the same loop without the two events on the lookup's dispatch
     noev_us = None
-    if shard is None and n_loc > 0 and fused:
+    if args.full and shard is None and n_loc > 0 and fused:
         for i in range(min(args.warmup, 3)):
             step(i, lookup_events=False)
         torch.cuda.synchronize()
@@ -369,7 +391,7 @@ def main():
 
     # ---- weak scaling: the 1-GPU point of the same family, run by rank 0 alone while the others wait ---------------
     extras = {}
-    if scaling == "weak" and world > 1:
+    if args.full and scaling == "weak" and world > 1:
         if rank == 0:
             W1 = syn.window_64_weak(1, args.seed)
             st1 = torch.cat([t(W1.poses).reshape(-1), t(W1.disps).reshape(-1)])
@@ -898,7 +920,7 @@ def main():
                    if args.steps and args.step_events else np.zeros(1))
         out["extra"] = {"dba_update_per_s": round(updates_per_s, 3),
                         "step_event_us": round(loop_event_us, 1),          # HIP events around the timed loop / steps
-                        "step_pooled_state_us": round(pooled_us, 1),       # the step without the per-step state reset
+                        "step_pooled_state_us": round(pooled_us, 1) if pooled_us else None,   # the step without the state reset
                         # the step without the two timing events on the lookup's dispatch (the roofline's live measurement is
                         # inside the timed region and costs `value` ~1 %: 250.4 against 254.1 us on three alternating runs)
                         "step_without_lookup_timing_events_us": round(noev_us, 1) if noev_us else None,
@@ -917,8 +939,8 @@ def main():
                         "step_us_p10_p50_p90": ([round(float(v), 1) for v in np.percentile(step_us, [10, 50, 90])]
                                                 if args.step_events else None),
                         "lookup_us_p10_p50_p90": [round(float(v), 1) for v in np.percentile(look_us, [10, 50, 90])],
-                        "ba_itrs2_us_p50": round(float(np.percentile(ba_us, 50)), 1),
-                        "gn_iter_GBps": round(gn_bytes / (float(np.percentile(ba_us, 50)) * 0.5e-6) / 1e9, 1),
+                        "ba_itrs2_us_p50": round(float(np.percentile(ba_us, 50)), 1) if nb else None,
+                        "gn_iter_GBps": round(gn_bytes / (float(np.percentile(ba_us, 50)) * 0.5e-6) / 1e9, 1) if nb else None,
                         **extras}
         if not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(W, fmaps, ii, jj)
@@ -941,6 +963,24 @@ def main():
         print(json.dumps(out))
     if dist is not None:
         dist.destroy_process_group()
+
+
+DUMP_MAX_ELEMS = 3 << 20   # per array (12 MB as float32): larger outputs are written as a fixed, seeded sample
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: the tensors the last timed step handed its caller -- poses and inverse depths after ba (in place),
+    the correlation features, coordinates and valid mask of the lookup -- as float32 <name>.npy.  An array of more than
+    DUMP_MAX_ELEMS elements (the correlation features: 77 M on the headline window) is written as `<name>_sample.npy`: the
+    elements at sorted flat indices drawn by a fixed seed from its size, the same for every run with the same arguments."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = a.detach()
+        if a.numel() > DUMP_MAX_ELEMS:
+            idx = np.unique(np.random.default_rng(20240).integers(0, a.numel(), DUMP_MAX_ELEMS))
+            a = a.reshape(-1)[torch.from_numpy(idx).to(a.device)]
+            name += "_sample"
+        np.save(os.path.join(out_dir, name + ".npy"), a.float().cpu().numpy())
 
 
 def cpu_baseline(W, fmaps, ii, jj, sample_edges=8):

@@ -3,7 +3,7 @@
 OUT=$PWD/gpurun_out; mkdir -p $OUT; REPO=$PWD
 timeout 300 ./scratch/solve_wave_test_bin > $OUT/r6_harness.txt 2>&1; echo "harness rc $?" >> $OUT/r6_harness.txt
 timeout 900 python -m pytest tests/test_gpu_solve.py -x -q -m gpu > $OUT/r6_test_solve.txt 2>&1; tail -5 $OUT/r6_test_solve.txt
-timeout 600 python bench.py --window 64_512 --steps 40 --warmup 10 --no-cpu-baseline > $OUT/r6_bench_64_512_a.json 2> $OUT/r6_bench_64_512_a.err
+timeout 600 python bench.py --full --window 64_512 --steps 40 --warmup 10 --no-cpu-baseline > $OUT/r6_bench_64_512_a.json 2> $OUT/r6_bench_64_512_a.err
 python - <<PY
 import json
 d=json.loads(open("$OUT/r6_bench_64_512_a.json").read().strip().splitlines()[-1])

@@ -1,7 +1,7 @@
 #!/bin/bash
 OUT=$PWD/gpurun_out; mkdir -p $OUT
 timeout 900 python -m pytest tests -q -m gpu -x -k "bacore or fusion or caller_sequence or compiled_adapter or sharded" 2>&1 | tail -4
-timeout 900 python bench.py --no-cpu-baseline > $OUT/r6_bench_a.json 2> $OUT/r6_bench_a.err
+timeout 900 python bench.py --full --no-cpu-baseline > $OUT/r6_bench_a.json 2> $OUT/r6_bench_a.err
 python - <<PY
 import json
 d=json.load(open("$OUT/r6_bench_a.json"))

@@ -1,6 +1,6 @@
 #!/bin/bash
 OUT=$PWD/gpurun_out
-timeout 900 python bench.py --no-cpu-baseline > $OUT/r6_bench_b.json 2> $OUT/r6_bench_b.err
+timeout 900 python bench.py --full --no-cpu-baseline > $OUT/r6_bench_b.json 2> $OUT/r6_bench_b.err
 python - <<PY
 import json
 d=json.load(open("$OUT/r6_bench_b.json"))

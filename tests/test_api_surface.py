@@ -1,83 +1,49 @@
 """Every `droid_backends.<name>` and every `lietorch` name the reference's Python uses resolves in the adapters
-(SURVEY.md section 8(b)).  Reads the reference tree, so it only runs where /root/reference is mounted."""
-import glob
+(SURVEY.md section 8(b)).  The names and parameter lists the reference uses are committed vectors
+(tests/golden/api_surface.json, scanned from the reference tree by tests/golden/make_api_surface.py; data only)."""
+import inspect
+import json
 import os
-import re
 
 import pytest
 
-REF = "/root/reference"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not mounted")
+
+@pytest.fixture(scope="module")
+def surface(golden_dir):
+    with open(os.path.join(golden_dir, "api_surface.json")) as fh:
+        return json.load(fh)
 
 
-def _sources():
-    files = glob.glob(os.path.join(REF, "dbaf", "**", "*.py"), recursive=True) + glob.glob(os.path.join(REF, "*.py"))
-    return [(f, open(f, errors="ignore").read()) for f in files]
-
-
-def test_every_droid_backends_attribute_the_reference_uses_exists():
+def test_every_droid_backends_attribute_the_reference_uses_exists(surface):
     import droid_backends
-    used = set()
-    for _, text in _sources():
-        used |= set(re.findall(r"\bdroid_backends\.([A-Za-z_]\w*)", text))
-    assert {"ba", "corr_index_forward", "frame_distance", "depth_filter", "iproj"} <= used  # the scan sees the call sites
+    used = set(surface["droid_backends_attrs"])
+    assert {"ba", "corr_index_forward", "frame_distance", "depth_filter", "iproj"} <= used  # the scan saw the call sites
     missing = sorted(n for n in used if not hasattr(droid_backends, n))
     assert not missing, missing
 
 
-def test_every_lietorch_name_the_reference_imports_exists():
+def test_every_lietorch_name_the_reference_imports_exists(surface):
     import lietorch
-    used = set()
-    for _, text in _sources():
-        for names in re.findall(r"from\s+lietorch\s+import\s+([^\n]+)", text):
-            used |= {n.strip() for n in names.replace("(", "").replace(")", "").split(",") if n.strip()}
+    used = set(surface["lietorch_imports"])
     assert "SE3" in used
     missing = sorted(n for n in used if not hasattr(lietorch, n))
     assert not missing, missing
     # the SE3 methods and attributes called on pose objects in the hot path and its callers
-    se3_used = set()
-    for _, text in _sources():
-        se3_used |= set(re.findall(r"\bSE3\.([A-Za-z_]\w*)", text))
-        se3_used |= set(re.findall(r"\bSE3\([^)]*\)\.([A-Za-z_]\w*)", text))
-        se3_used |= set(re.findall(r"\b(?:Gs?|Gij|Gi|Gj|poses|Ps?|dP|d)\s*(?:\[[^\]]*\])?\.(inv|retr|adjT|adj|matrix|translation|data|log|exp|scale|vec|cpu|act)\b", text))
-    missing = sorted(n for n in se3_used if not hasattr(lietorch.SE3, n) and n != "data")
+    missing = sorted(n for n in surface["se3_attrs"] if not hasattr(lietorch.SE3, n) and n != "data")
     assert not missing, missing
 
 
-def _ref_corr_module():
-    """the reference's dbaf/modules/corr.py imported with an empty stand-in for its native module"""
-    import importlib.util
-    import sys
-    import types
-    sys.dont_write_bytecode = True
-    saved = sys.modules.get("droid_backends")
-    sys.modules["droid_backends"] = types.ModuleType("droid_backends")
-    try:
-        spec = importlib.util.spec_from_file_location("_ref_modules_corr", os.path.join(REF, "dbaf", "modules", "corr.py"))
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-    finally:
-        if saved is not None:
-            sys.modules["droid_backends"] = saved
-        else:
-            del sys.modules["droid_backends"]
-    return mod
-
-
-def test_corr_mirrors_have_the_reference_signatures():
+def test_corr_mirrors_have_the_reference_signatures(surface):
     """dbaf_amd.corr is what INTEGRATION.md swaps in for `from modules.corr import CorrBlock, AltCorrBlock`
     (covisible_graph.py:7, motion_filter.py:8): every public name and every parameter list must match"""
-    import inspect
     from dbaf_amd import corr as mine
-    ref = _ref_corr_module()
-    for cls in ("CorrBlock", "AltCorrBlock", "CorrSampler", "CorrLayer"):
+    assert set(surface["corr_signatures"]) == {"CorrBlock", "AltCorrBlock", "CorrSampler", "CorrLayer"}
+    for cls, members in surface["corr_signatures"].items():
         assert hasattr(mine, cls), cls
-        rc, mc = getattr(ref, cls), getattr(mine, cls)
-        for name, member in inspect.getmembers(rc, predicate=inspect.isfunction):
-            if name.startswith("_") and name not in ("__init__", "__call__", "__getitem__"):
-                continue
+        mc = getattr(mine, cls)
+        assert "__init__" in members, cls
+        for name, rp in members.items():
             assert hasattr(mc, name), (cls, name)
-            rp = list(inspect.signature(member).parameters)
             mp = list(inspect.signature(getattr(mc, name)).parameters)
             assert mp[:len(rp)] == rp, (cls, name, rp, mp)   # the mirror may add trailing keyword options only
             extra = [inspect.signature(getattr(mc, name)).parameters[k] for k in mp[len(rp):]]
@@ -95,29 +61,20 @@ def _nparams(fn):
         return len([a for a in inner.split(",") if a.strip()]) if inner.strip() else 0
 
 
-def test_droid_backends_signatures_match_the_bindings():
+def test_droid_backends_signatures_match_the_bindings(surface):
     """src/droid.cpp: every m.def / class method bound there exists here with the same number of parameters -- in the
     package AND in the compiled adapter (csrc_ext/droid_backends_ext.cpp), which must be a drop-in by itself"""
-    import inspect
     import droid_backends
-    text = open(os.path.join(REF, "src", "droid.cpp")).read()
-    bound = re.findall(r'm\.def\("(\w+)",\s*&(\w+)', text)
+    bound = surface["bindings"]
     assert len(bound) >= 10
-    for pyname, cname in bound:
-        m = re.search(r"\b%s\s*\(([^)]*)\)\s*\{" % cname, text)
-        assert m, cname
-        nargs = len([a for a in m.group(1).split(",") if a.strip()])
+    for pyname, nargs in bound.items():
         fn = getattr(droid_backends, pyname)
         assert _nparams(fn) == nargs, (pyname, nargs)
         if droid_backends.compiled is not None and pyname != "ba_extend":   # (ba_extend: debug variant, Python only)
             assert _nparams(getattr(droid_backends.compiled, pyname)) == nargs, ("compiled", pyname, nargs)
-    methods = re.findall(r'\.def\("(\w+)",\s*&BACore::(\w+)\)', text)
-    assert {m for m, _ in methods} >= {"init", "hessian", "optimize", "retract"}
-    hdr = open(os.path.join(REF, "src", "bacore.h")).read()
-    for pyname, cname in methods:
-        m = re.search(r"\b%s\s*\(([^)]*)\)\s*;" % cname, hdr)
-        assert m, cname
-        nargs = len([a for a in m.group(1).split(",") if a.strip()])
+    methods = surface["bacore_methods"]
+    assert set(methods) >= {"init", "hessian", "optimize", "retract"}
+    for pyname, nargs in methods.items():
         fn = getattr(droid_backends.BACore, pyname)
         assert len(inspect.signature(fn).parameters) == nargs + 1, (pyname, nargs)  # + self
         if droid_backends.compiled is not None:

@@ -54,7 +54,7 @@ def _bench_ranks(world, *args):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
                         "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-                        "--gpus", str(world), "--steps", "4", "--warmup", "2", "--backend", "gloo", "--no-cpu-baseline",
+                        "--gpus", str(world), "--steps", "4", "--warmup", "2", "--backend", "gloo", "--full", "--no-cpu-baseline",
                         *args], env=env, capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
@@ -81,5 +81,25 @@ def test_bench_two_ranks_whole_path_weak_and_strong():
 
 
 def test_bench_reports_the_sharded_driver_overhead():
-    d = _bench(None, "--no-cpu-baseline")
+    d = _bench(None, "--full", "--no-cpu-baseline")
     assert "sharded_x1_overhead_us" in d["extra"]
+    assert d["extra"]["step_pooled_state_us"] > 0 and d["extra"]["ba_itrs2_us_p50"] > 0
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs: the last timed step's outputs as float32 .npy, at most 64 MB; the same inputs in every run (the
+    lookup is bit-exact, so its coordinates and features repeat), ms_per_step is the timed step"""
+    import numpy as np
+    got = []
+    for k in range(2):
+        d = _bench(None, "--dump-outputs", str(tmp_path / str(k)))
+        assert abs(d["value"] * d["ms_per_step"] - 1e3) < 1e-2 * 1e3
+        files = sorted(os.listdir(tmp_path / str(k)))
+        assert files == ["coords.npy", "corr_sample.npy", "disps.npy", "poses.npy", "valid.npy"], files
+        arrs = {f: np.load(tmp_path / str(k) / f) for f in files}
+        assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrs.values())
+        assert arrs["poses.npy"].shape[1] == 7 and arrs["coords.npy"].shape[-1] == 2
+        got.append(arrs)
+    for f in ("coords.npy", "corr_sample.npy", "valid.npy"):
+        assert np.array_equal(got[0][f], got[1][f]), f

@@ -15,7 +15,7 @@ for set in "SQ_VMEM_TA_ADDR_FIFO_FULL SQ_VMEM_TA_CMD_FIFO_FULL SQ_VMEM_WR_TA_DAT
            "TCP_UTCL1_STALL_INFLIGHT_MAX_sum TCP_UTCL1_STALL_MULTI_MISS_sum TCP_UTCL1_SERIALIZATION_STALL_sum TCP_UTCL1_THRASHING_STALL_sum" \
            "TCC_EA0_RDREQ_32B_sum TCC_EA0_RDREQ_64B_sum TCC_EA0_RDREQ_128B_sum TCC_EA0_WRREQ_64B_sum"; do
   i=$((i+1))
-  timeout 90 rocprofv3 --kernel-trace --pmc $set --output-format csv -d $OUT -o p$i -- python $REPO/bench.py --steps 3 --warmup 1 --no-cpu-baseline > $OUT/log$i.txt 2>&1
+  timeout 90 rocprofv3 --kernel-trace --pmc $set --output-format csv -d $OUT -o p$i -- python $REPO/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > $OUT/log$i.txt 2>&1
 done
 python - <<PY
 import csv, glob, collections

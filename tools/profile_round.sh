@@ -43,5 +43,5 @@ PY
 # the bench line last: it reads the traffic per launch from the round's PMC file under profiles/ (copied there on this box;
 # the builder commits the same file from gpurun_out/)
 cp $OUT/${TAG}_pmc_lookup$SFX.json $REPO/profiles/${TAG}_pmc_lookup$SFX.json
-timeout 600 python $REPO/bench.py $ARGS > $OUT/${TAG}_bench$SFX.json 2> $OUT/${TAG}_bench$SFX.err
+timeout 600 python $REPO/bench.py --full $ARGS > $OUT/${TAG}_bench$SFX.json 2> $OUT/${TAG}_bench$SFX.err
 cat $OUT/${TAG}_bench$SFX.json
