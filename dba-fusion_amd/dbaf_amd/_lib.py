@@ -119,6 +119,8 @@ SYMBOLS = {
     "dba_peer_exchange_open": (c_int, [_P, ctypes.POINTER(_P)]),
     "dba_peer_exchange_close": (c_int, [_P, c_int]),
     "dba_peer_allreduce_f64": (c_int, [_P, c_size_t, _P, c_int, c_int, ctypes.c_uint, c_size_t, _P, _P]),
+    "dba_cvx_upsample_disp": (c_int, [_P, c_int, _P, _P] + [c_int] * 4 + [_P, c_int, _P, _P]),
+    "dba_segment_reduce": (c_int, [_P, c_int, _P, c_int, ctypes.c_int64, ctypes.c_int64, c_int, c_int, _P, _P]),
 }
 
 _lib = None

@@ -572,6 +572,25 @@ int dba_depth_filter(const float *poses, const float *disps, const float *intrin
  *             region at index `rank`), `epoch` = 1, 2, 3, ... identical on all ranks and increasing by one per call,
  *             `status` a device int the kernel sets to DBA_PEER_TIMEOUT if a peer's contribution did not arrive within
  *             ~2 s (buf is left untouched then). */
+/* ---- the `--upsample` path (csrc/upsample.hip) -------------------------------------------------------------------
+ * convex upsampling of inverse depth: cvx_upsample with dim == 1 (dbaf/droid_net.py:17-31), called by
+ * DepthVideo.upsample (dbaf/depth_video.py:205-209) as disps_up[ix] = cvx_upsample(disps[ix], mask).
+ *   disps     [n_disps,ht,wd] f32;   mask [B,576,ht,wd] DBA_F32 or DBA_F16, channel = k*64 + a*8 + b with the 3x3 tap
+ *             k = ky*3+kx reading disps[y+ky-1, x+kx-1] (zero outside the map);
+ *   out       [n_out,8ht,8wd] f32 (16-byte aligned): out[dst, 8y+a, 8x+b] = sum_k softmax_k(mask[f,k*64+a*8+b,y,x]) * tap_k;
+ *   src_rows, dst_rows [B] int64 device row maps of mask frame f (NULL = identity); frames whose rows fall outside
+ *             [0,n_disps) / [0,n_out) are skipped.  A half mask rounds every weight to half before the product
+ *             (torch.softmax keeps the mask's dtype), the sum is float. */
+int dba_cvx_upsample_disp(const float *disps, int n_disps, const int64_t *src_rows, const void *mask, int mask_dtype,
+                          int B, int ht, int wd, float *out, int n_out, const int64_t *dst_rows, dba_stream_t stream);
+/* deterministic segmented sum / mean: torch_scatter.scatter_sum / scatter_mean with a 1-D index (dbaf/droid_net.py:14,65
+ * GraphAgg; dbaf/geom/ba.py:7).  src [outer,n,inner] dtype (DBA_F32 / DBA_F16), index [n] int64 ->
+ * out [outer,dim_size,inner]: out[o,s,i] = sum over e with index[e] == s of src[o,e,i], in ascending e, accumulated in
+ * float and rounded once; mean != 0 divides by max(count_s, 1).  Every element of out is written (empty slots = 0);
+ * index entries outside [0,dim_size) are ignored.  No atomics: bit-identical run to run. */
+int dba_segment_reduce(const void *src, int dtype, const int64_t *index, int n, int64_t outer, int64_t inner,
+                       int dim_size, int mean, void *out, dba_stream_t stream);
+
 #define DBA_PEER_TIMEOUT 1
 size_t dba_peer_exchange_bytes(size_t max_doubles);
 int dba_peer_exchange_create(size_t bytes, void **region, unsigned char *handle64);
