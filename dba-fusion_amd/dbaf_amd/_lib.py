@@ -121,6 +121,11 @@ SYMBOLS = {
     "dba_peer_allreduce_f64": (c_int, [_P, c_size_t, _P, c_int, c_int, ctypes.c_uint, c_size_t, _P, _P]),
     "dba_cvx_upsample_disp": (c_int, [_P, c_int, _P, _P] + [c_int] * 4 + [_P, c_int, _P, _P]),
     "dba_segment_reduce": (c_int, [_P, c_int, _P, c_int, ctypes.c_int64, ctypes.c_int64, c_int, c_int, _P, _P]),
+    "dba_frame_distance_bidir": (c_int, [_P] * 5 + [c_int] * 4 + [c_float, _P, _P]),
+    "dba_proximity_edges_capacity": (c_int, [c_int] * 5),
+    "dba_proximity_edges": (c_int, [_P] * 3 + [c_int] * 7 + [c_float, ctypes.c_double, c_int, c_int, _P, c_int, c_int]
+                            + [_P, _P, c_int, _P, _P, c_int, _P, _P]),
+    "dba_filter_repeated_edges": (c_int, [_P, _P, c_int, _P, _P, c_int, _P, _P, _P, _P]),
 }
 
 _lib = None

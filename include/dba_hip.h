@@ -591,6 +591,41 @@ int dba_cvx_upsample_disp(const float *disps, int n_disps, const int64_t *src_ro
 int dba_segment_reduce(const void *src, int dtype, const int64_t *index, int n, int64_t outer, int64_t inner,
                        int dim_size, int mean, void *out, dba_stream_t stream);
 
+/* ---- edge management of the covisibility graph (csrc/proximity.hip) ---------------------------------------------
+ * dba_frame_distance_bidir: DepthVideo.distance with bidirectional=True (dbaf/depth_video.py:240-270) in one launch:
+ *   dist[n] = .5f * (fd(ii[n],jj[n]) + fd(jj[n],ii[n])) in float, fd = dba_frame_distance's per-pair arithmetic, so the
+ *   result is bit-identical to two dba_frame_distance calls averaged in float32 (:255-261).  Pairs with an index outside
+ *   [0, n_frames) get NaN (nothing is read for them); n_frames = rows of poses and disps that may be read.
+ * dba_proximity_edges: CovisibleGraph.add_proximity_factors (dbaf/covisible_graph.py:357-441) up to its add_factors
+ *   call: the edge list es (:395-438), in the reference's order, for t = video.counter.value.  Candidates are
+ *   meshgrid(arange(t0,t), arange(t1,t)) row-major (cc = (t-t0)(t-t1)), then the skip extras (t-1, t0+s) for each s of
+ *   skip_edge_host[n_skip] with t0+s > 0 when (t-1) - t0 == frontend_window - 1 (:371-377).  Existing edges ex_ii/ex_jj
+ *   [n_ex] = cat(ii, ii_bad, ii_inac), cat(jj, jj_bad, jj_inac) (:383-384).  Distances use beta (:379); selection follows
+ *   :380-438 with thresh compared in double in the greedy pass (:412, d[k].item() > thresh) and in float32 for the skip
+ *   tail (:436); argsort ties go to the lower candidate index, NaN sorts after +inf.
+ *     dist   [cc + n_skip] f32 out: the candidates' distances after :380-381 (inf where ii - rad < jj, not computed, and
+ *            where d > 100), the extras after the grid;
+ *     edges  [2, capacity] int64 out: edges[0, 0..count) = ii, edges[1, 0..count) = jj;
+ *     count  one device int: the edge count, -1 if capacity was too small, -2 where the reference raises IndexError (a
+ *            stereo index below -len(d), :399).
+ *   capacity >= dba_proximity_edges_capacity(t, t0, rad, stereo, max_factors) = step 4's edges + max(max_factors,0) + 4.
+ *   Requires 0 <= t0 < t and 0 <= t1 < t; cc + n_skip > 8192 or n_skip > 16 is DBA_ERR_UNSUPPORTED.  Two launches.
+ * dba_filter_repeated_edges: CovisibleGraph.__filter_repeated_edges (dbaf/covisible_graph.py:61-72): out = the
+ *   proposals (ii, jj)[n] not in the existing list ex_ii/ex_jj [n_ex] = cat(ii, ii_inac), cat(jj, jj_inac), in order;
+ *   duplicates inside the proposals are kept, as the reference keeps them.  out_ii/out_jj [n], *count = kept edges.
+ * None of the three synchronises; none uses atomics (bit-identical run to run). */
+int dba_frame_distance_bidir(const float *poses, const float *disps, const float *intrinsics, const int64_t *ii,
+                             const int64_t *jj, int N, int n_frames, int ht, int wd, float beta, float *dist,
+                             dba_stream_t stream);
+int dba_proximity_edges_capacity(int t, int t0, int rad, int stereo, int max_factors);
+int dba_proximity_edges(const float *poses, const float *disps, const float *intrinsics, int ht, int wd, int t,
+                        int t0, int t1, int rad, int nms, float beta, double thresh, int max_factors, int stereo,
+                        const int *skip_edge_host, int n_skip, int frontend_window, const int64_t *ex_ii,
+                        const int64_t *ex_jj, int n_ex, float *dist, int64_t *edges, int capacity, int *count,
+                        dba_stream_t stream);
+int dba_filter_repeated_edges(const int64_t *ii, const int64_t *jj, int n, const int64_t *ex_ii, const int64_t *ex_jj,
+                              int n_ex, int64_t *out_ii, int64_t *out_jj, int *count, dba_stream_t stream);
+
 #define DBA_PEER_TIMEOUT 1
 size_t dba_peer_exchange_bytes(size_t max_doubles);
 int dba_peer_exchange_create(size_t bytes, void **region, unsigned char *handle64);
