@@ -29,6 +29,12 @@ class ShardExchange(ctypes.Structure):
                 ("n_all", c_int), ("send", c_void_p), ("recv", c_void_p)]
 
 
+class RowJob(ctypes.Structure):
+    """dba_row_job of include/dba_hip.h"""
+    _fields_ = [("src", c_void_p), ("dst", c_void_p), ("pos", c_void_p), ("row_bytes", ctypes.c_int64),
+                ("count", c_int), ("dst_row0", c_int), ("src_rows", c_int), ("dst_rows", c_int)]
+
+
 # every exported symbol of include/dba_hip.h with its (restype, argtypes); pointers are void*
 _P = c_void_p
 SYMBOLS = {
@@ -126,6 +132,11 @@ SYMBOLS = {
     "dba_proximity_edges": (c_int, [_P] * 3 + [c_int] * 7 + [c_float, ctypes.c_double, c_int, c_int, _P, c_int, c_int]
                             + [_P, _P, c_int, _P, _P, c_int, _P, _P]),
     "dba_filter_repeated_edges": (c_int, [_P, _P, c_int, _P, _P, c_int, _P, _P, _P, _P]),
+    "dba_select_edges": (c_int, [_P, _P, _P, c_int, c_int, _P, ctypes.c_int64, ctypes.c_int64, _P, _P, c_int, _P, _P, _P,
+                                 _P]),
+    "dba_move_rows": (c_int, [ctypes.POINTER(RowJob), c_int, _P]),
+    "dba_shift_rows": (c_int, [ctypes.POINTER(_P), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), c_int,
+                               ctypes.c_int64, _P]),
 }
 
 _lib = None

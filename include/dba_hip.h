@@ -626,6 +626,56 @@ int dba_proximity_edges(const float *poses, const float *disps, const float *int
 int dba_filter_repeated_edges(const int64_t *ii, const int64_t *jj, int n, const int64_t *ex_ii, const int64_t *ex_jj,
                               int n_ex, int64_t *out_ii, int64_t *out_jj, int *count, dba_stream_t stream);
 
+/* ---- retiring edges and dropping a keyframe (csrc/factors.hip) ---------------------------------------------------
+ * The caller's edge bookkeeping around the update: CovisibleGraph.rm_factors (dbaf/covisible_graph.py:152-176),
+ * rm_keyframe (:180-211), the frontend's retirement rule (dbaf/dbaf_frontend.py:235-239) and the edge statements of
+ * __rollup (dbaf/dbaf_frontend.py:106-117).  Integers and bytes only: every result is exact.
+ * dba_select_edges: one launch, one workgroup.  Decides for each edge p of (ii, jj, age)[n] whether it is dropped:
+ *     DBA_SEL_MASK      mask[p] != 0                                  (rm_factors' mask, one byte per edge)
+ *     DBA_SEL_RULE_OR   age > a  ||  (ii < b || jj < b)               (dbaf_frontend.py:238-239, a = max_age,
+ *     DBA_SEL_RULE_AND  age > a  &&  (ii < b || jj < b)                :235-236         b = t1 - active_window)
+ *     DBA_SEL_KEYFRAME  ii == a || jj == a, tested on the values as given; then every written entry >= a is
+ *                       decremented (covisible_graph.py:197-199, :207-210)
+ *     DBA_SEL_ROLL      ii - a < 0 || jj - a < 0; written entries are ii - a, jj - a (dbaf_frontend.py:108-112)
+ *     DBA_SEL_SHIFT     nothing is dropped; written entries are ii - a, jj - a (:106-107, :117-118)
+ *   and compacts both sides in the input's order (ballot + prefix sums, no atomics):
+ *     keep [3, n] int64 out: rows ii, jj, age of the kept edges (the age row is left alone when age == NULL);
+ *     drop [2, n_pre + n] int64 out: pre_ii / pre_jj [n_pre] copied to the front (rm_factors' torch.cat with the
+ *          inactive lists, :158-159), then ii, jj of the dropped edges;
+ *     sel  [2 + 2n] int32 out: n_keep, n_drop, the kept positions (n slots), the dropped positions (n slots): what the
+ *          host reads, in one copy, to size the results; sel + 2 and sel + 2 + n are position lists for dba_move_rows.
+ *   n > 8192 is DBA_ERR_UNSUPPORTED; n == 0 writes the two counts and copies pre.
+ * dba_move_rows: ONE launch that executes up to DBA_MAX_ROW_JOBS row copies
+ *     dst[(dst_row0 + r) * row_bytes ..] = src[(pos ? pos[r] : r) * row_bytes ..],  r in [0, count)
+ *   for payloads of different row sizes; a position outside [0, src_rows) copies nothing.  Each job moves with the
+ *   widest of 16 / 8 / 4 / 2 / 1 bytes that divides row_bytes and both base addresses.  Source and destination must
+ *   not overlap.  dst_row0 + count <= dst_rows is checked on the host.
+ * dba_shift_rows: ONE launch doing buf[ix] = buf[ix + 1] for up to DBA_MAX_SHIFT_BUFS buffers bases[k] of rows[k]
+ *   rows of row_bytes[k] bytes (rm_keyframe's nine statements, covisible_graph.py:185-195); needs 0 <= ix < rows - 1.
+ * The job and buffer tables are host arrays, passed to the kernel by value.  None of the three synchronises. */
+#define DBA_SEL_MASK 0
+#define DBA_SEL_RULE_OR 1
+#define DBA_SEL_RULE_AND 2
+#define DBA_SEL_KEYFRAME 3
+#define DBA_SEL_ROLL 4
+#define DBA_SEL_SHIFT 5
+#define DBA_SEL_MAX_EDGES 8192
+#define DBA_MAX_ROW_JOBS 8
+#define DBA_MAX_SHIFT_BUFS 12
+typedef struct dba_row_job {
+  const void *src;    /* device: first source row */
+  void *dst;          /* device: first destination row */
+  const int *pos;     /* device: count source positions, or NULL for rows 0..count-1 */
+  int64_t row_bytes;
+  int count, dst_row0, src_rows, dst_rows;
+} dba_row_job;
+int dba_select_edges(const int64_t *ii, const int64_t *jj, const int64_t *age, int n, int mode,
+                     const unsigned char *mask, int64_t a, int64_t b, const int64_t *pre_ii, const int64_t *pre_jj,
+                     int n_pre, int64_t *keep, int64_t *drop, int *sel, dba_stream_t stream);
+int dba_move_rows(const dba_row_job *jobs_host, int n_jobs, dba_stream_t stream);
+int dba_shift_rows(void *const *bases_host, const int64_t *row_bytes_host, const int64_t *rows_host, int n_bufs,
+                   int64_t ix, dba_stream_t stream);
+
 #define DBA_PEER_TIMEOUT 1
 size_t dba_peer_exchange_bytes(size_t max_doubles);
 int dba_peer_exchange_create(size_t bytes, void **region, unsigned char *handle64);
