@@ -59,9 +59,15 @@ struct BaPlan {  // host-side view of the workspace
   dba_ba_layout layout;
   size_t bytes;
   int P, N, B, HW, nchunks;
+  int ht, wd, t0, t1;   // the sizes it was planned for (P = t1 - t0, HW = ht * wd)
 };
 
 int ba_plan(int N, int B, int ht, int wd, int t0, int t1, void *ws, size_t ws_bytes, BaPlan *plan);
+// First statement of an extern "C" entry that works on a workspace: plans (and thereby validates) its N, B, ht, wd, t0, t1, ws,
+// ws_bytes -- the names these parameters have in every entry of include/dba_hip.h -- or returns ba_plan's error from the entry
+#define DBA_PLAN_OR_RETURN(plan) \
+  BaPlan plan;                   \
+  if (const int plan_rc_ = ::dba::ba_plan(N, B, ht, wd, t0, t1, ws, ws_bytes, &plan)) return plan_rc_
 
 // kernels (ba_kernels.hip / ba_solve.hip)
 constexpr int GKEY_MAGIC = 0x6b657935;   // first word of a valid graph key
@@ -100,27 +106,41 @@ __global__ void ba_schur_gram_kernel(const int64_t *ii, const int64_t *jj, const
 __global__ void ba_update_kernel(float *poses, const float *poses_src, float *disps, const int64_t *jj, const uint8_t *frame_owned,
                                  int HW, int t0, int P, int update_poses, int update_disps, float *dz_out,
                                  float *dx_out, BaTables T, BaBuffers W, float disp_floor);
-__global__ void ba_copy_dx_kernel(const double *src, float *dst, int n);
 __global__ void ba_copy_f32_kernel(const float *src, float *dst, int n);
 __global__ void ba_gather_edges_kernel(const float2 *tgt_inac, const float2 *wgt_inac, const int64_t *ii_inac, const int64_t *jj_inac,
                                        const int64_t *sel, int n_sel, int n_inac, const float2 *tgt_act, const float2 *wgt_act,
                                        const int64_t *ii_act, const int64_t *jj_act, int HW, float *tgt_out, float *wgt_out,
                                        int64_t *ii_out, int64_t *jj_out);
 
-// The Gauss-Newton loop of dba_ba (ba_host.hip), shared with the sharded sequence (ba_sharded_host.hip): frame_owned restricts
-// stages 1 / 2 / 4 to the rank's source frames, window_fpose is the COMPLETE graph's pose-level skyline for the redundant solve,
-// and `exchange` (may be null) runs between the reduction and the solve of every iteration on the summed-to-be [H | gap | b]
-// range of the workspace.  The back-substitution + retraction of iteration k ride in the linearisation of iteration k + 1 in
-// both uses (a rank only moves the depths of frames it owns; the poses' update is redundant on every rank).
+// What a BA call reads besides the state it moves (poses, disps), all on the device: camera, measurements and graph.
+struct BaProblem {
+  const float *intrinsics, *disps_sens, *targets, *weights, *eta;
+  int eta_rows;
+  const int64_t *ii, *jj;
+  const uint8_t *frame_owned;   // (may be null) restricts stages 1 / 2 / 4 to the rank's source frames: the sharded sequence
+};
 struct BaExchange {
   int (*fn)(void *ctx, double *hb, size_t hb_len, hipStream_t stream);
   void *ctx;
 };
-int ba_run_loop(float *poses, float *disps, const float *intrinsics, const float *disps_sens, const float *targets,
-                const float *weights, const float *eta, int eta_rows, const int64_t *ii, const int64_t *jj,
-                const uint8_t *frame_owned, int N, int B, int ht, int wd, int t0, int t1, int iterations, float lm, float ep,
-                float alpha, int motion_only, float *dx_out, float *dz_out, void *ws, size_t ws_bytes, dba_stream_t stream,
-                int prepared, int solver_hint, float disp_floor, const int32_t *window_fpose, const BaExchange *exchange);
+struct BaRun {
+  int iterations;
+  float lm, ep, alpha;
+  int motion_only;
+  // prepared = 1: the index tables in the workspace are those of this graph already (a previous dba_ba / dba_ba_prepare with the
+  // same ii, jj, sizes, t0, t1 and Schur form on this workspace): stage 0 is skipped.  prepared = 2: stage 0 decides that
+  // itself, on the device, by comparing the edge list with the key it left in the workspace (dba_ba_prepare_keyed).
+  int prepared, solver_hint;
+  float disp_floor;                // > 0: the last launch clamps the inverse depths of every frame of the buffer (dba_ba_run)
+  const int32_t *window_fpose;     // (may be null) the COMPLETE graph's pose-level skyline for a rank's redundant solve
+  const BaExchange *exchange;      // (may be null) runs between the reduction and the solve of every iteration on the
+                                   // summed-to-be [H | gap | b] range of the workspace
+  float *dx_out, *dz_out;          // (may be null) the last iteration's update
+};
+// The Gauss-Newton loop of dba_ba (ba_host.hip), shared with the sharded sequence (ba_sharded_host.hip).  The back-substitution +
+// retraction of iteration k ride in the linearisation of iteration k + 1 in both uses (a rank only moves the depths of frames
+// it owns; the poses' update is redundant on every rank).
+int ba_run_loop(const BaPlan &plan, const BaProblem &g, float *poses, float *disps, const BaRun &run, hipStream_t stream);
 
 // damped float64 Cholesky solve of H x = b, one workgroup
 // fpose: optional [n/6] skyline of the system at pose granularity (see BaTables); null = measure it from H

@@ -1715,11 +1715,6 @@ __global__ __launch_bounds__(256) void ba_gather_edges_kernel(const float2 *__re
   out[((size_t)o * 2 + 1) * HW + k] = v.y;
 }
 
-__global__ void ba_copy_dx_kernel(const double *__restrict__ src, float *__restrict__ dst, int n) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) dst[i] = (float)src[i];
-}
-
 __global__ void ba_copy_f32_kernel(const float *__restrict__ src, float *__restrict__ dst, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) dst[i] = src[i];

@@ -167,6 +167,7 @@ int dba_ba_sharded_run(float *poses, float *disps, const float *intrinsics, cons
   if (x->world > 1 && !x->comm && !x->peer_regions) return DBA_ERR_ARG;   // somebody has to carry the sums
   if (x->peer_regions && (!x->peer_status || !x->peer_epoch)) return DBA_ERR_ARG;
   if (x->band_len && (!x->band_idx || !x->band_buf)) return DBA_ERR_ARG;
+  DBA_PLAN_OR_RETURN(plan);
   hipStream_t s = (hipStream_t)stream;
   // The Gauss-Newton loop is dba_ba's own (ba_run_loop: the back-substitution + retraction of iteration k ride in the
   // linearisation of iteration k + 1 here too -- a rank only moves the depths of the frames it owns, the update of the poses
@@ -201,15 +202,19 @@ int dba_ba_sharded_run(float *poses, float *disps, const float *intrinsics, cons
     return DBA_OK;
   };
   const bool sums = x->world > 1 && (x->comm || x->peer_regions);
-  int rc = ba_run_loop(poses, disps, intrinsics, disps_sens, targets, weights, eta, eta_rows, ii, jj, frame_owned, N, B, ht, wd,
-                       t0, t1, iterations, lm, ep, alpha, motion_only, nullptr, nullptr, ws, ws_bytes, stream,
-                       (prepared == 1 || prepared == 2) ? prepared : 0, solver_hint, 0.f, window_fpose, sums ? &ex : nullptr);
+  BaProblem g;
+  g.intrinsics = intrinsics, g.disps_sens = disps_sens, g.targets = targets, g.weights = weights;
+  g.eta = eta, g.eta_rows = eta_rows, g.ii = ii, g.jj = jj, g.frame_owned = frame_owned;
+  BaRun run = {};   // (no floor on the depths, nobody asks for the last update)
+  run.iterations = iterations, run.lm = lm, run.ep = ep, run.alpha = alpha, run.motion_only = motion_only;
+  run.prepared = prepared, run.solver_hint = solver_hint, run.window_fpose = window_fpose, run.exchange = sums ? &ex : nullptr;
+  const int rc = ba_run_loop(plan, g, poses, disps, run, s);
   if (rc != DBA_OK) return rc;
   // the replicas of the depth maps are made coherent ONCE per call: every rank sends the rows it owns
   // (only with a communicator: the peer-read exchange carries the reduced system alone, its caller gathers the depths)
   if (!motion_only && iterations > 0 && x->kmax > 0 && x->comm) {
     if (!x->send || !x->recv || (x->n_mine && !x->my_rows) || (x->n_all && (!x->all_rows || !x->all_slots))) return DBA_ERR_ARG;
-    const int HW = ht * wd;
+    const int HW = plan.HW;
     if (x->n_mine) {
       hipLaunchKernelGGL(rows_pack_kernel, dim3((HW + 255) / 256, x->n_mine), dim3(256), 0, s, disps, x->my_rows, HW, x->send);
       DBA_LAUNCH_CHECK();

@@ -532,7 +532,7 @@ def test_ba_rejects_cpu_and_noncontiguous():
 
 def test_ba_three_and_four_iterations_match_the_oracle():
     """iterations > 2: the retracted window ping-pongs between the two workspace copies while back-substitution +
-    retraction ride in the next linearisation (csrc/ba_host.hip: ba_run); motion_only folds the pose part alone"""
+    retraction ride in the next linearisation (csrc/ba_host.hip: ba_run_loop); motion_only folds the pose part alone"""
     orc = _oracle()
     for itrs, motion_only in ((3, False), (4, False), (3, True)):
         W = syn.window_tiny_b(70 + itrs)
