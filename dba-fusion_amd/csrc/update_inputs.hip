@@ -1,0 +1,410 @@
+// The statements of CovisibleGraph.update() between the update operator and video.ba (dbaf/covisible_graph.py:229-230,
+// :242-247, :311-333, use_inactive=True), gfx950, two launches:
+//   edge pass     one workgroup of 1024 lanes, no atomics.  t0 = max(1, min(ii) + 1) (:230); the inactive edges inside
+//                 the window compacted in list order (wave ballots + prefix sums, :243) and the active list appended
+//                 (:244-245); min / max of the concatenated lists (:327-328 and depth_video.py:327-348); torch.unique of
+//                 the concatenated ii through a presence table in LDS (:330); one byte of flags per output edge: bit 0
+//                 short baseline (:317-321), bit 1 ii == max(ii) (:327), bit 2 jj == max(jj) (:328); a result block of
+//                 int32 words for the host and for the second launch.
+//   payload pass  grid over (output edge, pixel chunk) and (damping row, pixel chunk).  Reads the edge's row of target /
+//                 weight from the inactive or the active tensor ([n, ht, wd, 2], pixel-interleaved), applies the four
+//                 weight rules (:311-328) and writes the planar [N, 2, ht, wd] rows of :332-333; damping rows
+//                 0.2 * damping[kx[r]] + EP (:330).  It compares the counts the edge pass left with the counts its
+//                 outputs were sized for: on a mismatch it writes zeros and raises a pinned host word.
+// Arithmetic.  torch on the device divides a tensor by a host scalar as a multiplication with the scalar's float32
+// reciprocal (measured on the MI355X), one rounding per statement; `.2 * d + EP` is two kernels, two
+// roundings.  Every float operation here goes through an intrinsic the compiler neither contracts nor re-associates.
+#include <hip/hip_runtime.h>
+
+#include <stdint.h>
+#include <string.h>
+
+#include <mutex>
+
+#include "common.h"
+
+namespace dba {
+
+constexpr int UI_THREADS = 1024;
+constexpr int UI_WAVES = UI_THREADS / WAVE;
+constexpr int UI_PAY_THREADS = 256;
+constexpr int UI_FLAG_SHORT = 1, UI_FLAG_NEWEST_I = 2, UI_FLAG_NEWEST_J = 4;
+constexpr int UI_INDEX_CLAMP = 1 << 30;
+
+__device__ __forceinline__ float ui_mul(float a, float b) { return __fmul_rn(a, b); }
+__device__ __forceinline__ float ui_add(float a, float b) { return __fadd_rn(a, b); }
+__device__ __forceinline__ float ui_sub(float a, float b) { return __fsub_rn(a, b); }
+
+// lietorch shim, _cross / _qrot: each product and each difference is a torch kernel of its own
+__device__ __forceinline__ void ui_cross(const float *a, const float *b, float *c) {
+  c[0] = ui_sub(ui_mul(a[1], b[2]), ui_mul(a[2], b[1]));
+  c[1] = ui_sub(ui_mul(a[2], b[0]), ui_mul(a[0], b[2]));
+  c[2] = ui_sub(ui_mul(a[0], b[1]), ui_mul(a[1], b[0]));
+}
+
+// v + w * uv + cross(qv, uv), uv = 2 * cross(qv, v)
+__device__ __forceinline__ void ui_qrot(const float *q, const float *v, float *out) {
+  float uv[3], c[3];
+  ui_cross(q, v, uv);
+#pragma unroll
+  for (int k = 0; k < 3; k++) uv[k] = ui_mul(2.0f, uv[k]);
+  ui_cross(q, uv, c);
+#pragma unroll
+  for (int k = 0; k < 3; k++) out[k] = ui_add(ui_add(v[k], ui_mul(q[3], uv[k])), c[k]);
+}
+
+// || (T_i * T_j^-1).t ||: inv = (-qrot(qinv(q_j), t_j), qinv(q_j)), mul = qrot(q_i, t_B) + t_i.  The three squares are
+// summed as torch.norm's device reduction sums a row of three: (x^2 + z^2) + y^2.
+__device__ __forceinline__ float ui_baseline(const float *Pi, const float *Pj) {
+  const float qinv[4] = {-Pj[3], -Pj[4], -Pj[5], Pj[6]};
+  float r[3], t[3];
+  ui_qrot(qinv, Pj, r);
+#pragma unroll
+  for (int k = 0; k < 3; k++) r[k] = -r[k];
+  ui_qrot(Pi + 3, r, t);
+#pragma unroll
+  for (int k = 0; k < 3; k++) t[k] = ui_add(t[k], Pi[k]);
+  return __fsqrt_rn(ui_add(ui_add(ui_mul(t[0], t[0]), ui_mul(t[2], t[2])), ui_mul(t[1], t[1])));
+}
+
+template <bool IS_MIN>
+__device__ __forceinline__ int ui_block_minmax(int x, int *sh) {
+  x = wave_minmax<IS_MIN>(x);
+  if ((threadIdx.x & (WAVE - 1)) == 0) sh[threadIdx.x >> 6] = x;
+  __syncthreads();
+  int r = sh[0];
+#pragma unroll
+  for (int w = 1; w < UI_WAVES; w++) r = IS_MIN ? min(r, sh[w]) : max(r, sh[w]);
+  __syncthreads();
+  return r;
+}
+
+__device__ __forceinline__ int ui_clamp_index(int64_t v) {
+  return (int)(v > UI_INDEX_CLAMP ? UI_INDEX_CLAMP : (v < -UI_INDEX_CLAMP ? -UI_INDEX_CLAMP : v));
+}
+
+// Capacities (the host allocates them): sel [n_inac]; ii_out, jj_out, flags [n_inac + n_act]; kx [min(B, n_inac + n_act)];
+// res [DBA_UI_RES_WORDS].
+__global__ __launch_bounds__(UI_THREADS) void update_inputs_edge_kernel(
+    const int64_t *__restrict__ ii_inac, const int64_t *__restrict__ jj_inac, int n_inac,
+    const int64_t *__restrict__ ii_act, const int64_t *__restrict__ jj_act, int n_act, const float *__restrict__ poses,
+    int B, int has_t0, int64_t t0_arg, int64_t inac_range, float mask_threshold, int baseline_rule,
+    int *__restrict__ sel, int64_t *ii_out, int64_t *jj_out, unsigned char *__restrict__ flags,
+    int64_t *__restrict__ kx, int *__restrict__ res) {
+  __shared__ int wcount[UI_WAVES];
+  __shared__ int red[UI_WAVES];
+  __shared__ unsigned char present[DBA_UI_MAX_FRAMES];
+  const int tid = threadIdx.x, lane = tid & (WAVE - 1), wv = tid >> 6;
+  present[tid] = 0;  // (DBA_UI_MAX_FRAMES == UI_THREADS)
+
+  // :230, over the ACTIVE list alone
+  int64_t t0 = t0_arg;
+  if (!has_t0) {
+    int m = UI_INDEX_CLAMP;
+    for (int p = tid; p < n_act; p += UI_THREADS) m = min(m, ui_clamp_index(ii_act[p]));
+    m = ui_block_minmax<true>(m, red);
+    t0 = m + 1 > 1 ? m + 1 : 1;
+  } else {
+    __syncthreads();
+  }
+  const int64_t oldest = t0 - inac_range;
+
+  int lo_i = UI_INDEX_CLAMP, lo_j = UI_INDEX_CLAMP, hi_i = -UI_INDEX_CLAMP, hi_j = -UI_INDEX_CLAMP, bad = 0;
+  // :243-245, the inactive edges inside the window, in list order
+  int kept = 0;  // in the tiles before this one
+  for (int start = 0; start < n_inac; start += UI_THREADS) {
+    const int p = start + tid;
+    int64_t i = 0, j = 0;
+    bool k = false;
+    if (p < n_inac) {
+      i = ii_inac[p];
+      j = jj_inac[p];
+      k = i >= oldest && j >= oldest;
+    }
+    const uint64_t m = __ballot(k);
+    if (lane == 0) wcount[wv] = __popcll(m);
+    __syncthreads();
+    int before = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < UI_WAVES; w++) {
+      const int s = wcount[w];
+      if (w < wv) before += s;
+      total += s;
+    }
+    __syncthreads();
+    if (k) {
+      const int q = kept + before + __popcll(m & ((1ull << lane) - 1ull));
+      sel[q] = p;
+      ii_out[q] = i;
+      jj_out[q] = j;
+      const int ci = ui_clamp_index(i), cj = ui_clamp_index(j);
+      lo_i = min(lo_i, ci), hi_i = max(hi_i, ci), lo_j = min(lo_j, cj), hi_j = max(hi_j, cj);
+      if (i >= 0 && i < B) present[i] = 1;
+      if (i < 0 || i >= B || j < 0 || j >= B) bad = 1;
+    }
+    kept += total;
+  }
+  const int n_sel = kept, N = n_sel + n_act;
+  for (int p = tid; p < n_act; p += UI_THREADS) {
+    const int64_t i = ii_act[p], j = jj_act[p];
+    ii_out[n_sel + p] = i;
+    jj_out[n_sel + p] = j;
+    const int ci = ui_clamp_index(i), cj = ui_clamp_index(j);
+    lo_i = min(lo_i, ci), hi_i = max(hi_i, ci), lo_j = min(lo_j, cj), hi_j = max(hi_j, cj);
+    if (i >= 0 && i < B) present[i] = 1;
+    if (i < 0 || i >= B || j < 0 || j >= B) bad = 1;
+  }
+  // (the barriers inside also order the writes of ii_out / jj_out / present before the reads below)
+  lo_i = ui_block_minmax<true>(lo_i, red);
+  lo_j = ui_block_minmax<true>(lo_j, red);
+  hi_i = ui_block_minmax<false>(hi_i, red);
+  hi_j = ui_block_minmax<false>(hi_j, red);
+  bad = ui_block_minmax<false>(bad, red);
+
+  // :330, torch.unique(ii): the frames present, ascending
+  int n_kx;
+  {
+    const bool k = present[tid] != 0;
+    const uint64_t m = __ballot(k);
+    if (lane == 0) wcount[wv] = __popcll(m);
+    __syncthreads();
+    int before = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < UI_WAVES; w++) {
+      const int s = wcount[w];
+      if (w < wv) before += s;
+      total += s;
+    }
+    if (k) kx[before + __popcll(m & ((1ull << lane) - 1ull))] = tid;
+    n_kx = total;
+  }
+
+  // :317-321, :327-328
+  for (int e = tid; e < N; e += UI_THREADS) {
+    const int64_t i = ii_out[e], j = jj_out[e];
+    int f = 0;
+    if (baseline_rule && i >= 0 && i < B && j >= 0 && j < B) {
+      float Pi[7], Pj[7];
+#pragma unroll
+      for (int k = 0; k < 7; k++) { Pi[k] = poses[7 * i + k]; Pj[k] = poses[7 * j + k]; }
+      if (ui_baseline(Pi, Pj) < mask_threshold) f |= UI_FLAG_SHORT;
+    }
+    if (ui_clamp_index(i) == hi_i) f |= UI_FLAG_NEWEST_I;
+    if (ui_clamp_index(j) == hi_j) f |= UI_FLAG_NEWEST_J;
+    flags[e] = (unsigned char)f;
+  }
+  if (tid == 0) {
+    res[0] = (int)(t0 > UI_INDEX_CLAMP ? UI_INDEX_CLAMP : (t0 < -UI_INDEX_CLAMP ? -UI_INDEX_CLAMP : t0));
+    res[1] = n_sel;
+    res[2] = N;
+    res[3] = n_kx;
+    res[4] = lo_i;
+    res[5] = hi_i;
+    res[6] = lo_j;
+    res[7] = hi_j;
+    res[8] = bad;  // an index outside [0, B): the host raises
+  }
+}
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+struct PayloadArgs {
+  const float *target_inac, *weight_inac, *target_act, *weight_act, *disps, *damping;
+  const int *sel, *res;
+  const int64_t *ii_out, *kx;
+  const unsigned char *flags;
+  float *target_out, *weight_out, *damping_out;
+  int *status;  // pinned host words
+  int n_inac, n_act, B, HW, chunks, exp_n_sel, exp_N, exp_n_kx, far_rule;
+  float far_threshold, ep;
+};
+
+constexpr float UI_INV_1000 = 1.0f / 1000.0f, UI_INV_10 = 1.0f / 10.0f, UI_INV_4 = 1.0f / 4.0f, UI_FIFTH = 0.2f;
+
+__device__ __forceinline__ float ui_weight(float w, bool far_px, int f) {
+  if (far_px) w = ui_mul(w, UI_INV_1000);                 // :314
+  if (f & UI_FLAG_SHORT) w = ui_mul(w, UI_INV_1000);      // :322
+  if (f & UI_FLAG_NEWEST_I) w = ui_mul(w, UI_INV_10);     // :327
+  if (f & UI_FLAG_NEWEST_J) w = ui_mul(w, UI_INV_4);      // :328
+  return w;
+}
+
+// PIX pixels per lane: 4 where ht * wd is a multiple of 4 (16-byte loads and stores throughout), else 1 (an odd map
+// leaves every other edge row 8-byte aligned only)
+template <int PIX>
+__global__ __launch_bounds__(UI_PAY_THREADS) void update_inputs_payload_kernel(PayloadArgs a) {
+  const int HW = a.HW;
+  const bool ok = a.res[1] == a.exp_n_sel && a.res[2] == a.exp_N && a.res[3] == a.exp_n_kx && a.res[8] == 0;
+  if (!ok && blockIdx.x == 0 && threadIdx.x == 0) {
+    a.status[1] = a.res[1], a.status[2] = a.res[2], a.status[3] = a.res[3];
+    a.status[4] = a.exp_n_sel, a.status[5] = a.exp_N, a.status[6] = a.exp_n_kx;
+    __threadfence_system();
+    a.status[0] = 1;
+  }
+  const unsigned bid = blockIdx.x;
+  const unsigned row = bid / (unsigned)a.chunks, chunk = bid - row * (unsigned)a.chunks;
+  const int p0 = ((int)chunk * UI_PAY_THREADS + (int)threadIdx.x) * PIX;
+  if (p0 >= HW) return;
+  if ((int)row >= a.exp_N) {  // a damping row
+    const int r = (int)row - a.exp_N;
+    if (r >= a.exp_n_kx) return;
+    float *dst = a.damping_out + (long long)r * HW + p0;
+    const int64_t fr = ok ? a.kx[r] : -1;
+    if (PIX == 4) {
+      f32x4 d = {a.ep, a.ep, a.ep, a.ep};
+      if (fr >= 0 && fr < a.B) {
+        d = *(const f32x4 *)(a.damping + fr * HW + p0);
+#pragma unroll
+        for (int k = 0; k < 4; k++) d[k] = ui_add(ui_mul(UI_FIFTH, d[k]), a.ep);
+      }
+      *(f32x4 *)dst = d;
+    } else {
+      *dst = (fr >= 0 && fr < a.B) ? ui_add(ui_mul(UI_FIFTH, a.damping[fr * HW + p0]), a.ep) : a.ep;
+    }
+    return;
+  }
+  const int e = (int)row;
+  float *tx = a.target_out + (long long)e * 2 * HW + p0, *ty = tx + HW;
+  float *wx = a.weight_out + (long long)e * 2 * HW + p0, *wy = wx + HW;
+  // the edge's source row: inactive row sel[e] or active row e - n_sel
+  const float *ts = nullptr, *ws = nullptr;
+  if (ok) {
+    if (e < a.exp_n_sel) {
+      const int s = a.sel[e];
+      if (s >= 0 && s < a.n_inac) ts = a.target_inac + (long long)s * 2 * HW, ws = a.weight_inac + (long long)s * 2 * HW;
+    } else if (e - a.exp_n_sel < a.n_act) {
+      ts = a.target_act + (long long)(e - a.exp_n_sel) * 2 * HW, ws = a.weight_act + (long long)(e - a.exp_n_sel) * 2 * HW;
+    }
+  }
+  if (!ts) {  // the guard: zero weights leave ba's state as it is
+    if (PIX == 4) {
+      const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+      *(f32x4 *)tx = z, *(f32x4 *)ty = z, *(f32x4 *)wx = z, *(f32x4 *)wy = z;
+    } else {
+      *tx = 0.f, *ty = 0.f, *wx = 0.f, *wy = 0.f;
+    }
+    return;
+  }
+  const int f = a.flags[e];
+  const int64_t i = a.ii_out[e];
+  const bool far_on = a.far_rule && i >= 0 && i < a.B;
+  if (PIX == 4) {
+    const f32x4 t0 = *(const f32x4 *)(ts + 2 * p0), t1 = *(const f32x4 *)(ts + 2 * p0 + 4);
+    const f32x4 w0 = *(const f32x4 *)(ws + 2 * p0), w1 = *(const f32x4 *)(ws + 2 * p0 + 4);
+    f32x4 d = {0.f, 0.f, 0.f, 0.f};
+    if (far_on) d = *(const f32x4 *)(a.disps + i * HW + p0);
+    const bool fp0 = far_on && d[0] < a.far_threshold, fp1 = far_on && d[1] < a.far_threshold;
+    const bool fp2 = far_on && d[2] < a.far_threshold, fp3 = far_on && d[3] < a.far_threshold;
+    const f32x4 ox = {t0[0], t0[2], t1[0], t1[2]}, oy = {t0[1], t0[3], t1[1], t1[3]};
+    const f32x4 vx = {ui_weight(w0[0], fp0, f), ui_weight(w0[2], fp1, f), ui_weight(w1[0], fp2, f), ui_weight(w1[2], fp3, f)};
+    const f32x4 vy = {ui_weight(w0[1], fp0, f), ui_weight(w0[3], fp1, f), ui_weight(w1[1], fp2, f), ui_weight(w1[3], fp3, f)};
+    *(f32x4 *)tx = ox, *(f32x4 *)ty = oy, *(f32x4 *)wx = vx, *(f32x4 *)wy = vy;
+  } else {
+    const f32x2 t = *(const f32x2 *)(ts + 2 * p0), w = *(const f32x2 *)(ws + 2 * p0);
+    const bool fp = far_on && a.disps[i * HW + p0] < a.far_threshold;
+    *tx = t[0], *ty = t[1];
+    *wx = ui_weight(w[0], fp, f), *wy = ui_weight(w[1], fp, f);
+  }
+}
+
+// the pinned, host-coherent words a mismatch is reported through (sticky until polled): [0] raised, [1..3] the counts
+// of the edge pass, [4..6] the counts the outputs were sized for
+struct UiStatus {
+  std::mutex mu;
+  int *words = nullptr;
+};
+static UiStatus &ui_status() {
+  static UiStatus s;
+  return s;
+}
+
+}  // namespace dba
+
+using namespace dba;
+
+extern "C" {
+
+int dba_update_inputs_edges(const int64_t *ii_inac, const int64_t *jj_inac, int n_inac, const int64_t *ii_act,
+                            const int64_t *jj_act, int n_act, const float *poses, int n_frames, int has_t0, int64_t t0,
+                            int64_t inac_range, float mask_threshold, int baseline_rule, int *sel, int64_t *ii_out,
+                            int64_t *jj_out, unsigned char *flags, int64_t *kx, int *res, dba_stream_t stream) {
+  if (n_inac < 0 || n_act <= 0 || n_frames <= 0 || !ii_act || !jj_act || !ii_out || !jj_out || !flags || !kx || !res)
+    return DBA_ERR_ARG;
+  if (n_inac > 0 && (!ii_inac || !jj_inac || !sel)) return DBA_ERR_ARG;
+  if (baseline_rule && !poses) return DBA_ERR_ARG;
+  if (n_inac > DBA_SEL_MAX_EDGES || n_act > DBA_SEL_MAX_EDGES || n_frames > DBA_UI_MAX_FRAMES) return DBA_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(update_inputs_edge_kernel, dim3(1), dim3(UI_THREADS), 0, (hipStream_t)stream, ii_inac, jj_inac,
+                     n_inac, ii_act, jj_act, n_act, poses, n_frames, has_t0 ? 1 : 0, t0, inac_range, mask_threshold,
+                     baseline_rule ? 1 : 0, sel, ii_out, jj_out, flags, kx, res);
+  DBA_LAUNCH_CHECK();
+  return DBA_OK;
+}
+
+int dba_update_inputs_payload(const float *target_inac, const float *weight_inac, int n_inac, const float *target_act,
+                              const float *weight_act, int n_act, const float *disps, const float *damping,
+                              int n_frames, int ht, int wd, float far_threshold, int far_rule, float ep, const int *sel,
+                              const int64_t *ii_out, const unsigned char *flags, const int64_t *kx, const int *res,
+                              int exp_n_sel, int exp_N, int exp_n_kx, float *target_out, float *weight_out,
+                              float *damping_out, dba_stream_t stream) {
+  if (n_inac < 0 || n_act <= 0 || n_frames <= 0 || ht <= 0 || wd <= 0 || (int64_t)ht * wd > (1 << 24)) return DBA_ERR_ARG;
+  if (exp_n_sel < 0 || exp_n_sel > n_inac || exp_N < 0 || exp_N > n_inac + n_act || exp_n_kx < 0 ||
+      exp_n_kx > n_frames || exp_n_kx > n_inac + n_act)
+    return DBA_ERR_ARG;  // the edge pass's buffers hold n_inac + n_act edges and min(n_frames, that) frames
+  if (!target_act || !weight_act || !damping || !ii_out || !flags || !kx || !res) return DBA_ERR_ARG;
+  if (n_inac > 0 && (!target_inac || !weight_inac || !sel)) return DBA_ERR_ARG;
+  if (far_rule && !disps) return DBA_ERR_ARG;
+  if ((exp_N > 0 && (!target_out || !weight_out)) || (exp_n_kx > 0 && !damping_out)) return DBA_ERR_ARG;
+  if (n_inac > DBA_SEL_MAX_EDGES || n_act > DBA_SEL_MAX_EDGES || n_frames > DBA_UI_MAX_FRAMES) return DBA_ERR_UNSUPPORTED;
+  UiStatus &st = ui_status();
+  {
+    std::lock_guard<std::mutex> lock(st.mu);
+    if (!st.words) {
+      void *p = nullptr;
+      DBA_HIP_CHECK(hipHostMalloc(&p, sizeof(int) * DBA_UI_RES_WORDS,
+                                  hipHostMallocCoherent | hipHostMallocMapped | hipHostMallocPortable));
+      memset(p, 0, sizeof(int) * DBA_UI_RES_WORDS);
+      st.words = static_cast<int *>(p);
+    }
+  }
+  PayloadArgs a{};
+  a.target_inac = target_inac, a.weight_inac = weight_inac, a.target_act = target_act, a.weight_act = weight_act;
+  a.disps = disps, a.damping = damping, a.sel = sel, a.res = res, a.ii_out = ii_out, a.kx = kx, a.flags = flags;
+  a.target_out = target_out, a.weight_out = weight_out, a.damping_out = damping_out, a.status = st.words;
+  a.n_inac = n_inac, a.n_act = n_act, a.B = n_frames, a.HW = ht * wd;
+  a.exp_n_sel = exp_n_sel, a.exp_N = exp_N, a.exp_n_kx = exp_n_kx, a.far_rule = far_rule ? 1 : 0;
+  a.far_threshold = far_threshold, a.ep = ep;
+  const uint64_t rows = (uint64_t)exp_N + (uint64_t)exp_n_kx;
+  if (rows == 0) return DBA_OK;
+  const uintptr_t align = (uintptr_t)target_inac | (uintptr_t)weight_inac | (uintptr_t)target_act | (uintptr_t)weight_act |
+                          (uintptr_t)disps | (uintptr_t)damping | (uintptr_t)target_out | (uintptr_t)weight_out |
+                          (uintptr_t)damping_out;
+  if (align % 8) return DBA_ERR_ARG;
+  const bool wide = a.HW % 4 == 0 && align % 16 == 0;
+  const int per_wg = UI_PAY_THREADS * (wide ? 4 : 1);
+  a.chunks = (a.HW + per_wg - 1) / per_wg;
+  const uint64_t wgs = rows * (uint64_t)a.chunks;
+  if (wgs > (uint64_t)INT32_MAX) return DBA_ERR_UNSUPPORTED;
+  if (wide)
+    hipLaunchKernelGGL(update_inputs_payload_kernel<4>, dim3((unsigned)wgs), dim3(UI_PAY_THREADS), 0,
+                       (hipStream_t)stream, a);
+  else
+    hipLaunchKernelGGL(update_inputs_payload_kernel<1>, dim3((unsigned)wgs), dim3(UI_PAY_THREADS), 0,
+                       (hipStream_t)stream, a);
+  DBA_LAUNCH_CHECK();
+  return DBA_OK;
+}
+
+int dba_update_inputs_poll(int *counts6) {
+  UiStatus &st = ui_status();
+  std::lock_guard<std::mutex> lock(st.mu);
+  if (!st.words) return 0;
+  volatile int *w = st.words;
+  if (!w[0]) return 0;
+  if (counts6)
+    for (int k = 0; k < 6; k++) counts6[k] = w[1 + k];
+  w[0] = 0;
+  return 1;
+}
+
+}  // extern "C"

@@ -137,6 +137,11 @@ SYMBOLS = {
     "dba_move_rows": (c_int, [ctypes.POINTER(RowJob), c_int, _P]),
     "dba_shift_rows": (c_int, [ctypes.POINTER(_P), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), c_int,
                                ctypes.c_int64, _P]),
+    "dba_update_inputs_edges": (c_int, [_P, _P, c_int, _P, _P, c_int, _P, c_int, c_int, ctypes.c_int64, ctypes.c_int64,
+                                        c_float, c_int] + [_P] * 7),
+    "dba_update_inputs_payload": (c_int, [_P, _P, c_int, _P, _P, c_int, _P, _P, c_int, c_int, c_int, c_float, c_int,
+                                          c_float] + [_P] * 5 + [c_int] * 3 + [_P] * 4),
+    "dba_update_inputs_poll": (c_int, [ctypes.POINTER(c_int)]),
 }
 
 _lib = None

@@ -676,6 +676,55 @@ int dba_move_rows(const dba_row_job *jobs_host, int n_jobs, dba_stream_t stream)
 int dba_shift_rows(void *const *bases_host, const int64_t *row_bytes_host, const int64_t *rows_host, int n_bufs,
                    int64_t ix, dba_stream_t stream);
 
+/* ---- the VIO update's BA inputs (csrc/update_inputs.hip) ------------------------------------------------------------
+ * What CovisibleGraph.update(use_inactive=True) computes between the update operator and video.ba
+ * (dbaf/covisible_graph.py:229-230, :242-247, :311-333), and the four .item() reads of DepthVideo.ba
+ * (dbaf/depth_video.py:327-348), in two launches and no host synchronisation of their own.
+ * dba_update_inputs_edges: one launch, one workgroup, no atomics.  From the inactive lists (ii_inac, jj_inac)[n_inac], the
+ *   active lists (ii_act, jj_act)[n_act >= 1] and poses [n_frames, 7]:
+ *     t0       has_t0 ? t0 : max(1, min(ii_act) + 1)                                                      (:229-230)
+ *     sel      [n_inac] int32 out: the positions p with ii_inac[p] >= t0 - inac_range && jj_inac[p] >= t0 - inac_range,
+ *              in list order (:243); n_sel of them
+ *     ii_out, jj_out [n_inac + n_act] int64 out: the selected inactive edges, then the active ones (:244-245);
+ *              N = n_sel + n_act entries are written
+ *     kx       [min(n_frames, n_inac + n_act)] int64 out: torch.unique(ii_out), n_kx entries (:330)
+ *     flags    [n_inac + n_act] bytes out, N written: bit 0 baseline_rule && ||(T_i * T_j^-1).t|| < mask_threshold with
+ *              T = SE3(poses[.]), float32 in the operation order of the lietorch shim (:317-321); bit 1
+ *              ii_out[e] == max(ii_out) (:327); bit 2 jj_out[e] == max(jj_out) (:328)
+ *     res      [DBA_UI_RES_WORDS] int32 out: t0, n_sel, N, n_kx, min(ii_out), max(ii_out), min(jj_out), max(jj_out),
+ *              and [8] = 1 when an index lies outside [0, n_frames) (such an edge gets no baseline flag and no row in kx)
+ *   n_inac, n_act > 8192 or n_frames > DBA_UI_MAX_FRAMES is DBA_ERR_UNSUPPORTED; n_act == 0 is DBA_ERR_ARG.
+ *   Called alone it serves as the count query: res is all a host needs to size the outputs.
+ * dba_update_inputs_payload: one launch over (output edge, pixel chunk) and (damping row, pixel chunk).  target / weight
+ *   rows [n, ht, wd, 2] f32 of the inactive and active tensors -> the planar [exp_N, 2, ht, wd] rows of :332-333, target
+ *   unchanged, weight through, in this order and one float32 rounding each (a division by a host scalar is, on the
+ *   device, a product with the scalar's float32 reciprocal -- what torch's kernels do):
+ *       far_rule && disps[ii_out[e], p] < far_threshold  -> w * (1/1000)        (:311-314)
+ *       flags[e] & 1                                     -> w * (1/1000)        (:317-322)
+ *       flags[e] & 2                                     -> w * (1/10)          (:327)
+ *       flags[e] & 4                                     -> w * (1/4)           (:328)
+ *   and damping_out[r] = 0.2f * damping[kx[r]] + ep, two roundings, r < exp_n_kx (:330).  exp_n_sel, exp_N, exp_n_kx are
+ *   the counts the outputs were sized for (they fix the grid); the kernel compares them with res[1..3] as the edge pass
+ *   of THIS call left them.  On a mismatch (or res[8]) it writes zero target and weight rows and damping = ep -- a ba
+ *   call with zero weights changes nothing -- and raises a pinned host word; it reads and writes nothing outside
+ *   [0, exp_N) / [0, exp_n_kx) rows.  Pointers must be 8-byte aligned; 16-byte loads and stores where ht * wd is a multiple
+ *   of 4 and the pointers allow.
+ * dba_update_inputs_poll: 1 when a payload pass reported a mismatch since the last poll (counts6 = the edge pass's n_sel,
+ *   N, n_kx, then the expected three), else 0.  Reads pinned host memory: no device synchronisation. */
+#define DBA_UI_MAX_FRAMES 1024
+#define DBA_UI_RES_WORDS 16
+int dba_update_inputs_edges(const int64_t *ii_inac, const int64_t *jj_inac, int n_inac, const int64_t *ii_act,
+                            const int64_t *jj_act, int n_act, const float *poses, int n_frames, int has_t0, int64_t t0,
+                            int64_t inac_range, float mask_threshold, int baseline_rule, int *sel, int64_t *ii_out,
+                            int64_t *jj_out, unsigned char *flags, int64_t *kx, int *res, dba_stream_t stream);
+int dba_update_inputs_payload(const float *target_inac, const float *weight_inac, int n_inac, const float *target_act,
+                              const float *weight_act, int n_act, const float *disps, const float *damping,
+                              int n_frames, int ht, int wd, float far_threshold, int far_rule, float ep, const int *sel,
+                              const int64_t *ii_out, const unsigned char *flags, const int64_t *kx, const int *res,
+                              int exp_n_sel, int exp_N, int exp_n_kx, float *target_out, float *weight_out,
+                              float *damping_out, dba_stream_t stream);
+int dba_update_inputs_poll(int *counts6);
+
 #define DBA_PEER_TIMEOUT 1
 size_t dba_peer_exchange_bytes(size_t max_doubles);
 int dba_peer_exchange_create(size_t bytes, void **region, unsigned char *handle64);
