@@ -218,6 +218,24 @@ std::vector<torch::Tensor> gather_edges(torch::Tensor target_inac, torch::Tensor
   return {ii_n, jj_n, tg, wt};
 }
 
+// Shapes the geometry kernels rely on and cannot see (they read poses[index], disps[index] and intrinsics[0..3] unchecked, like
+// the reference): tensor metadata only, no device read, no synchronisation.  The index VALUES stay the caller's responsibility.
+// The edge functions (ii given) read poses[ii], poses[jj] only and may be handed the poses of the frames in use next to the whole
+// depth buffer; iproj and depth_filter read a pose for every frame of disps.
+void check_geom(const char *op, const torch::Tensor &poses, const torch::Tensor &disps, const torch::Tensor &intrinsics,
+                const torch::Tensor *ii = nullptr, const torch::Tensor *jj = nullptr, const torch::Tensor *ix = nullptr,
+                const torch::Tensor *thresh = nullptr) {
+  TORCH_CHECK(disps.dim() == 3, op, ": disps must be [B, ht, wd]");
+  if (ii || ix) TORCH_CHECK(poses.dim() == 2 && poses.size(1) == 7, op, ": poses must be [B, 7]");
+  if (!ii)
+    TORCH_CHECK(poses.dim() >= 1 && poses.size(0) >= disps.size(0) && poses.numel() >= 7 * disps.size(0), op, ": poses has ",
+                poses.dim() >= 1 ? poses.size(0) : 0, " rows, fewer than the ", disps.size(0), " frames of disps");
+  TORCH_CHECK(intrinsics.numel() >= 4, op, ": intrinsics must hold (fx, fy, cx, cy), got ", intrinsics.numel(), " elements");
+  if (ii) TORCH_CHECK(ii->sizes() == jj->sizes(), op, ": ii and jj must have one shape");
+  if (ix) TORCH_CHECK(ix->dim() >= 1 && thresh->dim() >= 1 && thresh->size(0) == ix->size(0), op,
+                      ": thresh must have one entry per index of ix");
+}
+
 // frame_distance (src/droid.cpp:181-197)
 torch::Tensor frame_distance(torch::Tensor poses, torch::Tensor disps, torch::Tensor intrinsics, torch::Tensor ii,
                              torch::Tensor jj, const float beta) {
@@ -226,6 +244,7 @@ torch::Tensor frame_distance(torch::Tensor poses, torch::Tensor disps, torch::Te
   CHECK_INPUT(intrinsics);
   CHECK_INPUT(ii);
   CHECK_INPUT(jj);
+  check_geom("frame_distance", poses, disps, intrinsics, &ii, &jj);
   const int N = (int)ii.size(0);
   torch::Tensor dist = torch::empty({N}, poses.options());   // (every entry is written by its workgroup)
   check(dba_frame_distance(poses.data_ptr<float>(), disps.data_ptr<float>(), intrinsics.data_ptr<float>(), ii.data_ptr<int64_t>(),
@@ -243,6 +262,7 @@ std::vector<torch::Tensor> projmap(torch::Tensor poses, torch::Tensor disps, tor
   CHECK_INPUT(intrinsics);
   CHECK_INPUT(ii);
   CHECK_INPUT(jj);
+  check_geom("projmap", poses, disps, intrinsics, &ii, &jj);
   const int N = (int)ii.size(0), ht = (int)disps.size(1), wd = (int)disps.size(2);
   torch::Tensor coords = torch::zeros({N, ht, wd, 3}, poses.options());
   torch::Tensor valid = torch::zeros({N, ht, wd, 1}, poses.options());
@@ -257,6 +277,7 @@ torch::Tensor iproj(torch::Tensor poses, torch::Tensor disps, torch::Tensor intr
   CHECK_INPUT(poses);
   CHECK_INPUT(disps);
   CHECK_INPUT(intrinsics);
+  check_geom("iproj", poses, disps, intrinsics);
   const int nm = (int)disps.size(0), ht = (int)disps.size(1), wd = (int)disps.size(2);
   torch::Tensor points = torch::zeros({nm, ht, wd, 3}, disps.options());
   check(dba_iproj(poses.data_ptr<float>(), disps.data_ptr<float>(), intrinsics.data_ptr<float>(), nm, ht, wd,
@@ -273,6 +294,7 @@ torch::Tensor depth_filter(torch::Tensor poses, torch::Tensor disps, torch::Tens
   CHECK_INPUT(intrinsics);
   CHECK_INPUT(ix);
   CHECK_INPUT(thresh);
+  check_geom("depth_filter", poses, disps, intrinsics, nullptr, nullptr, &ix, &thresh);
   const int num = (int)ix.size(0), nbuf = (int)disps.size(0), ht = (int)disps.size(1), wd = (int)disps.size(2);
   torch::Tensor counter = torch::zeros({num, ht, wd}, disps.options());
   check(dba_depth_filter(poses.data_ptr<float>(), disps.data_ptr<float>(), intrinsics.data_ptr<float>(), ix.data_ptr<int64_t>(),

@@ -29,8 +29,15 @@ def projective_transform(poses, depths, intrinsics, ii, jj):
     d = depths.reshape(-1, depths.shape[-2], depths.shape[-1]).float().contiguous()
     K = intrinsics.reshape(-1, 4).float().contiguous()
     B, ht, wd = d.shape
-    if K.shape[0] == 1:
+    # (the kernel reads poses[i], poses[j] and intrinsics[i], intrinsics[j] unchecked: shapes only, no device read)
+    if pdata.shape[0] < B:
+        raise RuntimeError("projective_transform: poses has %d rows, fewer than the %d frames of depths" % (pdata.shape[0], B))
+    if K.shape[0] not in (1, B):
+        raise RuntimeError("projective_transform: intrinsics must have 1 or %d rows of (fx, fy, cx, cy), got %d" % (B, K.shape[0]))
+    if K.shape[0] == 1 and B != 1:
         K = K.expand(B, 4).contiguous()
+    if ii.shape != jj.shape:
+        raise RuntimeError("projective_transform: ii and jj must have one shape, got %s and %s" % (tuple(ii.shape), tuple(jj.shape)))
     ii = ii.to(device=d.device, dtype=torch.int64).contiguous()
     jj = jj.to(device=d.device, dtype=torch.int64).contiguous()
     N = int(ii.shape[0])

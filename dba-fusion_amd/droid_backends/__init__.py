@@ -538,11 +538,33 @@ class BACore:
         return [dx, dz_full[:_num_kx(self.eta, self.ii, self.t0, self.t1, self.ht, self.wd)]]
 
 
+def _check_geom(op, poses, disps, intrinsics, ii=None, jj=None, ix=None, thresh=None, every_frame=True):
+    """Shapes the geometry kernels rely on and cannot see (they read poses[index], disps[index] and intrinsics[0..3] unchecked,
+    like the reference): host-side metadata only, no device read, no synchronisation.  The INDEX VALUES stay the caller's
+    responsibility, as in the reference.  every_frame: the kernel reads a pose for every frame of disps (iproj) or for any
+    neighbour inside the buffer (depth_filter); the edge functions read poses[ii], poses[jj] only, and DepthVideo.distance
+    style callers hand them the poses of the frames in use next to the whole depth buffer."""
+    if disps.dim() != 3:
+        raise RuntimeError("%s: disps must be [B, ht, wd], got %s" % (op, tuple(disps.shape)))
+    if (ii is not None or ix is not None) and (poses.dim() != 2 or poses.shape[1] != 7):
+        raise RuntimeError("%s: poses must be [B, 7], got %s" % (op, tuple(poses.shape)))
+    if every_frame and (poses.numel() < 7 * disps.shape[0] or poses.shape[0] < disps.shape[0]):
+        raise RuntimeError("%s: poses has %d rows, fewer than the %d frames of disps" % (op, poses.shape[0], disps.shape[0]))
+    if intrinsics.numel() < 4:
+        raise RuntimeError("%s: intrinsics must hold (fx, fy, cx, cy), got %d elements" % (op, intrinsics.numel()))
+    if ii is not None and ii.shape != jj.shape:
+        raise RuntimeError("%s: ii and jj must have one shape, got %s and %s" % (op, tuple(ii.shape), tuple(jj.shape)))
+    if ix is not None and (thresh.dim() < 1 or ix.dim() < 1 or thresh.shape[0] != ix.shape[0]):
+        raise RuntimeError("%s: thresh must have one entry per index of ix, got %s and %s"
+                           % (op, tuple(thresh.shape), tuple(ix.shape)))
+
+
 def frame_distance(poses, disps, intrinsics, ii, jj, beta):
     """droid.cpp:181-197."""
     for x, nm, dt in ((poses, "poses", torch.float32), (disps, "disps", torch.float32),
                       (intrinsics, "intrinsics", torch.float32), (ii, "ii", torch.int64), (jj, "jj", torch.int64)):
         _check(x, nm, dt)
+    _check_geom("frame_distance", poses, disps, intrinsics, ii=ii, jj=jj, every_frame=False)
     N = int(ii.shape[0])
     _, ht, wd = disps.shape
     dist = torch.empty(N, dtype=torch.float32, device=poses.device)     # (every entry is written by its workgroup)
@@ -557,6 +579,7 @@ def projmap(poses, disps, intrinsics, ii, jj):
     for x, nm, dt in ((poses, "poses", torch.float32), (disps, "disps", torch.float32),
                       (intrinsics, "intrinsics", torch.float32), (ii, "ii", torch.int64), (jj, "jj", torch.int64)):
         _check(x, nm, dt)
+    _check_geom("projmap", poses, disps, intrinsics, ii=ii, jj=jj, every_frame=False)
     N = int(ii.shape[0])
     _, ht, wd = disps.shape
     coords = torch.zeros(N, ht, wd, 3, dtype=torch.float32, device=poses.device)
@@ -572,6 +595,7 @@ def depth_filter(poses, disps, intrinsics, ix, thresh):
                       (intrinsics, "intrinsics", torch.float32), (ix, "ix", torch.int64),
                       (thresh, "thresh", torch.float32)):
         _check(x, nm, dt)
+    _check_geom("depth_filter", poses, disps, intrinsics, ix=ix, thresh=thresh)
     num = int(ix.shape[0])
     nbuf, ht, wd = disps.shape
     counter = torch.zeros(num, ht, wd, dtype=disps.dtype, device=disps.device)
@@ -585,6 +609,7 @@ def iproj(poses, disps, intrinsics):
     """droid.cpp:218-227."""
     for x, nm in ((poses, "poses"), (disps, "disps"), (intrinsics, "intrinsics")):
         _check(x, nm, torch.float32)
+    _check_geom("iproj", poses, disps, intrinsics)
     nm_, ht, wd = disps.shape
     points = torch.zeros(nm_, ht, wd, 3, dtype=disps.dtype, device=disps.device)
     _lib.check(_lib.load().dba_iproj(_ptr(poses), _ptr(disps), _ptr(intrinsics), int(nm_), int(ht), int(wd),
