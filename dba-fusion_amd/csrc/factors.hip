@@ -12,7 +12,8 @@
 //     sides therefore come out in the input's order, which is the order boolean indexing gives.  No atomics.
 //   - row mover: a job table passed by value in the kernel arguments; the grid is the concatenation of every job's
 //     (row, chunk) pairs, a chunk being 1024 elements of the job's vector width (16 KB at 16 bytes), four loads in
-//     flight per lane before the first store.  Pure streaming: no LDS, plain vector stores.
+//     flight per lane before the first store.  Pure streaming: no LDS, plain vector stores.  (The table and the
+//     copy body are in row_jobs.h, which add_factors.hip shares.)
 //   - row shift: the same body over a table of one-row jobs.
 // Nothing synchronises the host; the selection leaves its counts and position lists in one small buffer.
 #include <hip/hip_runtime.h>
@@ -20,13 +21,11 @@
 #include <stdint.h>
 
 #include "common.h"
+#include "row_jobs.h"
 
 namespace dba {
 
 constexpr int SEL_THREADS = 1024;
-constexpr int MOVE_THREADS = 256;
-constexpr int MOVE_UNROLL = 4;
-constexpr int MOVE_CHUNK = MOVE_THREADS * MOVE_UNROLL;  // elements of the job's width per workgroup
 
 __global__ __launch_bounds__(SEL_THREADS) void select_edges_kernel(
     const int64_t *__restrict__ ii, const int64_t *__restrict__ jj, const int64_t *__restrict__ age, int n, int mode,
@@ -101,70 +100,6 @@ __global__ __launch_bounds__(SEL_THREADS) void select_edges_kernel(
   }
 }
 
-struct RowJobDev {
-  const char *src;
-  char *dst;
-  const int *pos;
-  long long row_elems;  // row bytes / width
-  int count, dst_row0, src_rows, width;
-  unsigned wg_start, chunks;  // first workgroup of the job; workgroups per row
-};
-
-template <int N>
-struct RowTable {
-  RowJobDev j[N];
-  int n;
-};
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-template <typename T>
-__device__ __forceinline__ void copy_chunk(const char *s, char *d, long long n, unsigned chunk) {
-  const T *sp = (const T *)s;
-  T *dp = (T *)d;
-  const long long e0 = (long long)chunk * MOVE_CHUNK + threadIdx.x;
-  T v[MOVE_UNROLL];
-  if ((long long)(chunk + 1) * MOVE_CHUNK <= n) {
-#pragma unroll
-    for (int u = 0; u < MOVE_UNROLL; u++) v[u] = sp[e0 + u * MOVE_THREADS];
-#pragma unroll
-    for (int u = 0; u < MOVE_UNROLL; u++) dp[e0 + u * MOVE_THREADS] = v[u];
-  } else {
-#pragma unroll
-    for (int u = 0; u < MOVE_UNROLL; u++)
-      if (e0 + u * MOVE_THREADS < n) v[u] = sp[e0 + u * MOVE_THREADS];
-#pragma unroll
-    for (int u = 0; u < MOVE_UNROLL; u++)
-      if (e0 + u * MOVE_THREADS < n) dp[e0 + u * MOVE_THREADS] = v[u];
-  }
-}
-
-// the workgroup's (job, row, chunk) and its copy.  The table is read with constant indices and the job picked by
-// selects, so it stays in scalar registers (a dynamic index could send it through private memory).
-template <int N>
-__device__ __forceinline__ void run_row_jobs(const RowTable<N> &t) {
-  const unsigned bid = blockIdx.x;
-  RowJobDev J = t.j[0];
-#pragma unroll
-  for (int q = 1; q < N; q++)
-    if (q < t.n && bid >= t.j[q].wg_start) J = t.j[q];
-  const unsigned local = bid - J.wg_start;
-  const unsigned r = local / J.chunks, c = local - r * J.chunks;
-  if ((int)r >= J.count) return;
-  const int srow = J.pos ? J.pos[r] : (int)r;
-  if (srow < 0 || srow >= J.src_rows) return;
-  const long long row_bytes = J.row_elems * J.width;
-  const char *s = J.src + srow * row_bytes;
-  char *d = J.dst + (long long)(J.dst_row0 + (int)r) * row_bytes;
-  switch (J.width) {
-    case 16: copy_chunk<u32x4>(s, d, J.row_elems, c); break;
-    case 8: copy_chunk<uint64_t>(s, d, J.row_elems, c); break;
-    case 4: copy_chunk<uint32_t>(s, d, J.row_elems, c); break;
-    case 2: copy_chunk<uint16_t>(s, d, J.row_elems, c); break;
-    default: copy_chunk<uint8_t>(s, d, J.row_elems, c); break;
-  }
-}
-
 __global__ __launch_bounds__(MOVE_THREADS) void row_mover_kernel(RowTable<DBA_MAX_ROW_JOBS> t) { run_row_jobs(t); }
 
 __global__ __launch_bounds__(MOVE_THREADS) void row_shift_kernel(RowTable<DBA_MAX_SHIFT_BUFS> t) { run_row_jobs(t); }
@@ -172,37 +107,6 @@ __global__ __launch_bounds__(MOVE_THREADS) void row_shift_kernel(RowTable<DBA_MA
 }  // namespace dba
 
 using namespace dba;
-
-namespace {
-
-int vector_width(const void *s, const void *d, int64_t row_bytes) {
-  const uint64_t x = (uint64_t)(uintptr_t)s | (uint64_t)(uintptr_t)d | (uint64_t)row_bytes;
-  for (int w = 16; w > 1; w >>= 1)
-    if (x % w == 0) return w;
-  return 1;
-}
-
-// appends the job to the table; false if the grid would pass 2^31 - 1 workgroups
-template <int N>
-bool push_job(RowTable<N> &t, uint64_t &wgs, const char *src, char *dst, const int *pos, int64_t row_bytes, int count,
-              int dst_row0, int src_rows) {
-  RowJobDev &J = t.j[t.n];
-  J.src = src;
-  J.dst = dst;
-  J.pos = pos;
-  J.width = vector_width(src, dst, row_bytes);
-  J.row_elems = row_bytes / J.width;
-  J.count = count;
-  J.dst_row0 = dst_row0;
-  J.src_rows = src_rows;
-  J.chunks = (unsigned)((J.row_elems + MOVE_CHUNK - 1) / MOVE_CHUNK);
-  J.wg_start = (unsigned)wgs;
-  wgs += (uint64_t)J.chunks * (uint64_t)count;
-  t.n++;
-  return wgs <= (uint64_t)INT32_MAX;
-}
-
-}  // namespace
 
 extern "C" {
 

@@ -35,6 +35,17 @@ class RowJob(ctypes.Structure):
                 ("count", c_int), ("dst_row0", c_int), ("src_rows", c_int), ("dst_rows", c_int)]
 
 
+class AfJob(ctypes.Structure):
+    """dba_af_job of include/dba_hip.h"""
+    _fields_ = [("kind", c_int), ("reserved", c_int), ("rows", RowJob)]
+
+
+class AfGeometry(ctypes.Structure):
+    """dba_af_geometry of include/dba_hip.h"""
+    _fields_ = [("poses", c_void_p), ("disps", c_void_p), ("intrinsics_b4", c_void_p), ("ii", c_void_p), ("jj", c_void_p),
+                ("n_frames", c_int), ("ht", c_int), ("wd", c_int), ("reserved", c_int)]
+
+
 # every exported symbol of include/dba_hip.h with its (restype, argtypes); pointers are void*
 _P = c_void_p
 SYMBOLS = {
@@ -137,6 +148,8 @@ SYMBOLS = {
     "dba_move_rows": (c_int, [ctypes.POINTER(RowJob), c_int, _P]),
     "dba_shift_rows": (c_int, [ctypes.POINTER(_P), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), c_int,
                                ctypes.c_int64, _P]),
+    "dba_add_factors_plan": (c_int, [_P, _P, _P, c_int, _P, _P, c_int, _P, _P, c_int] + [c_int] * 4 + [_P, _P, _P, _P]),
+    "dba_add_factors_payload": (c_int, [ctypes.POINTER(AfJob), c_int, ctypes.POINTER(AfGeometry), _P]),
     "dba_update_inputs_edges": (c_int, [_P, _P, c_int, _P, _P, c_int, _P, c_int, c_int, ctypes.c_int64, ctypes.c_int64,
                                         c_float, c_int] + [_P] * 7),
     "dba_update_inputs_payload": (c_int, [_P, _P, c_int, _P, _P, c_int, _P, _P, c_int, c_int, c_int, c_float, c_int,

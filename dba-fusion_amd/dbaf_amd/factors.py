@@ -4,6 +4,8 @@
   retire_edges(graph, max_age, oldest, mode)      the frontend's statement dbaf/dbaf_frontend.py:235-239, mask included
   rm_keyframe(graph, ix)                          drop-in for CovisibleGraph.rm_keyframe (dbaf/covisible_graph.py:180-211)
   shift_edges(graph, roll)                        the edge statements of __rollup (dbaf/dbaf_frontend.py:106-118)
+  add_factors(graph, ii, jj, remove=False)        drop-in for CovisibleGraph.add_factors (dbaf/covisible_graph.py:102-149)
+  add_neighborhood_factors(graph, t0, t1, r=3)    drop-in for CovisibleGraph.add_neighborhood_factors (:344-354)
 
 and their explicit-tensor forms select_edges, move_rows and shift_rows, for callers without the reference's objects.
 HIP kernels in csrc/factors.hip: a selection is one launch of one workgroup (a stable compaction of ii, jj, age: the
@@ -16,6 +18,11 @@ The drop-ins read and assign the attributes of a CovisibleGraph-shaped object as
 NEW tensors wherever the reference assigns new ones.  One difference: where the reference renumbers in place
 (`self.ii[self.ii >= ix] -= 1`, `self.graph.ii -= roll`) they assign new tensors too and leave the old ones unwritten, so
 a holder of the old tensor object does not see the renumbering; nothing in the reference keeps such a holder.
+
+add_factors (csrc/add_factors.hip) is one plan launch of one workgroup (the repeated-edge filter, the eviction mask, the
+final lists and the gathers' source rows, every proposed frame index range-checked), the call's one host read, and one
+payload launch for every row the call moves or produces: kept rows, the inactive store, the gathers from the video, the
+new target rows (reprojected in the kernel) and the zeroed weight rows.  The volume build stays CorrBlock's.
 
 `stats` counts the launches and host reads of this module since import (as CorrBlock.stats does for the pyramid).
 """
@@ -30,7 +37,11 @@ MAX_ROW_JOBS = 8       # per move_rows call
 MAX_SHIFT_BUFS = 12    # per shift_rows call
 SEL_MASK, SEL_RULE_OR, SEL_RULE_AND, SEL_KEYFRAME, SEL_ROLL, SEL_SHIFT = range(6)
 
-stats = dict(select_launches=0, mover_launches=0, shift_launches=0, host_reads=0)
+MAX_ADD_JOBS = 16      # row jobs per add_factors payload launch (plus the reprojection)
+AF_COPY, AF_GATHER, AF_ZERO, AF_REPROJECT = range(4)
+AF_INFO_WORDS = 8
+
+stats = dict(select_launches=0, mover_launches=0, shift_launches=0, host_reads=0, plan_launches=0, payload_launches=0)
 
 
 def _ptr(x):
@@ -378,3 +389,214 @@ def shift_edges(graph, roll):
     launches = move_rows(jobs)
     _commit(graph, None, out)
     return dict(kept_inactive=si.n_keep, dropped_inactive=si.n_drop, mover_launches=launches)
+
+
+# ---- adding edges ---------------------------------------------------------------------------------------------------
+
+def _proposal(op, dev, ii, jj):
+    """the proposed edges as device int64 lists; host sequences and CPU tensors go up in ONE copy"""
+    on_dev = [isinstance(x, torch.Tensor) and x.is_cuda for x in (ii, jj)]
+    if all(on_dev):
+        out = [x.to(device=dev, dtype=torch.long).reshape(-1).contiguous() for x in (ii, jj)]
+    else:
+        host = [torch.as_tensor(x.cpu() if d else x).to(torch.long).reshape(-1) for x, d in zip((ii, jj), on_dev)]
+        _require(host[0].shape == host[1].shape, op, "ii and jj must have one length")
+        both = torch.stack(host).to(dev)
+        out = [both[0], both[1]]
+    _require(out[0].shape == out[1].shape, op, "ii and jj must have one length")
+    return out
+
+
+def _video_rows(op, x, nm, dev, dtype=None):
+    _require(isinstance(x, torch.Tensor) and x.is_cuda and x.device == dev, op,
+             "video.%s must be a HIP device tensor on %s; no CPU path" % (nm, dev))
+    _require(x.dim() >= 2 and x.is_contiguous(), op, "video.%s must be contiguous with its frames along dim 0" % nm)
+    _require(dtype is None or x.dtype == dtype, op, "video.%s must be %s, got %s" % (nm, dtype, x.dtype))
+    return x
+
+
+def _af_job(table, k, kind, src, dst, pos, count, dst_row0):
+    """fills table[k]; src / dst are [rows, ...] views, pos an int32 device tensor or None"""
+    j = table[k]
+    j.kind = kind
+    r = j.rows
+    row_bytes = dst.element_size()
+    for d in dst.shape[1:]:
+        row_bytes *= int(d)
+    r.src = src.data_ptr() if src is not None else None
+    r.dst, r.pos = dst.data_ptr(), (pos.data_ptr() if pos is not None else None)
+    r.row_bytes, r.count, r.dst_row0 = row_bytes, int(count), int(dst_row0)
+    r.src_rows, r.dst_rows = (int(src.shape[0]) if src is not None else 0), int(dst.shape[0])
+
+
+def add_factors(graph, ii, jj, remove=False):
+    """CovisibleGraph.add_factors (dbaf/covisible_graph.py:102-149).  ii, jj: the proposed edges, device int64 tensors,
+    CPU tensors or host sequences (host inputs are uploaded in one copy).  In the reference's order:
+      filter   every proposal already in (graph.ii, graph.jj) or (graph.ii_inac, graph.jj_inac) is dropped (the *_bad
+               lists are not consulted, duplicates inside the proposal stay, the order stays); when nothing is left the
+               call returns and assigns nothing;
+      evict    when max_factors > 0, N + n_new > max_factors, graph.corr is not None and `remove`: the edges of the mask
+               `argsort(age) >= max_factors - n_new` -- a mask over POSITIONS k, true where the index argsort(age)[k] is
+               at or past the limit; a negative limit drops every edge -- go to the back of the inactive lists with their
+               target / weight rows (rm_factors(mask, store=True)); the kept edges keep their order.  The reference's
+               device argsort leaves the order of equal ages unspecified; HERE TIES RESOLVE TO THE LOWER POSITION (a
+               stable sort).  The filter sees the lists as they were before the eviction;
+      append   ii, jj, age (zeros), net = video.nets[ii], target = video.reproject(ii, jj) (bit-identical to
+               projective_transform with the video's per-frame intrinsics), weight = zeros; with corr_impl == "volume"
+               also inp = video.inps[ii] and corr = corr[kept].cat(CorrBlock(fmaps[ii, 0], fmaps[jj, ii == jj])).  Where
+               graph.corr / net / inp is None the new tensors become the attribute.
+    New tensors are assigned; the old ones are not written.  One plan launch, ONE host read, one payload launch (the
+    volume build is CorrBlock's).  A proposed frame index outside the video's rows raises ValueError after the read,
+    before any payload work is enqueued and with the graph as it was.
+    Returns dict(added, filtered, evicted, plan_launches, payload_launches, host_reads)."""
+    from .corr import CorrBlock
+    op = "add_factors"
+    _check_list(op, None, graph.ii, "graph.ii")
+    dev = graph.ii.device
+    for nm in ("jj", "age", "ii_inac", "jj_inac"):
+        _check_list(op, dev, getattr(graph, nm), "graph." + nm)
+    n, m = int(graph.ii.shape[0]), int(graph.ii_inac.shape[0])
+    _require(graph.jj.shape[0] == n and graph.age.shape[0] == n, op, "graph.ii, jj and age must have one length")
+    _require(graph.jj_inac.shape[0] == m, op, "graph.ii_inac and jj_inac must have one length")
+    volume = graph.corr_impl == "volume"
+    corr = graph.corr
+    _require(corr is None or isinstance(corr, CorrBlock), op,
+             "graph.corr must be a dbaf_amd.corr.CorrBlock, got %s" % type(corr).__name__)
+    v = graph.video
+    poses = _video_rows(op, v.poses, "poses", dev, torch.float32)
+    disps = _video_rows(op, v.disps, "disps", dev, torch.float32)
+    intr = _video_rows(op, v.intrinsics, "intrinsics", dev, torch.float32)
+    nets = _video_rows(op, v.nets, "nets", dev)
+    _require(poses.dim() == 2 and poses.shape[1] == 7, op, "video.poses must be [B, 7], got %s" % (tuple(poses.shape),))
+    _require(disps.dim() == 3, op, "video.disps must be [B, ht, wd], got %s" % (tuple(disps.shape),))
+    _require(intr.dim() == 2 and intr.shape[1] == 4, op, "video.intrinsics must be [B, 4], got %s" % (tuple(intr.shape),))
+    ht, wd = int(disps.shape[1]), int(disps.shape[2])
+    frames = [poses, disps, intr, nets]
+    inps = fmaps = None
+    cams = 1
+    if volume:
+        inps = _video_rows(op, v.inps, "inps", dev)
+        fmaps = _video_rows(op, v.fmaps, "fmaps", dev)
+        _require(fmaps.dim() == 5, op, "video.fmaps must be [B, cams, C, h, w], got %s" % (tuple(fmaps.shape),))
+        cams = int(fmaps.shape[1])
+        frames += [inps, fmaps]
+    n_frames = min(int(x.shape[0]) for x in frames)
+    target, weight = _payload(op, graph.target, "target", n), _payload(op, graph.weight, "weight", n)
+    for nm, x in (("target", target), ("weight", weight)):
+        _require(x.dtype == torch.float32 and tuple(x.shape[2:]) == (ht, wd, 2), op,
+                 "graph.%s must be float32 [1, N, %d, %d, 2], got %s %s" % (nm, ht, wd, x.dtype, tuple(x.shape)))
+    net = inp = None
+    if graph.net is not None:
+        net = _payload(op, graph.net, "net", n)
+        _require(net.dtype == nets.dtype and net.shape[2:] == nets.shape[1:], op,
+                 "graph.net rows %s %s differ from video.nets' %s %s" % (tuple(net.shape[2:]), net.dtype,
+                                                                         tuple(nets.shape[1:]), nets.dtype))
+    if volume and graph.inp is not None:
+        inp = _payload(op, graph.inp, "inp", n)
+        _require(inp.dtype == inps.dtype and inp.shape[2:] == inps.shape[1:], op,
+                 "graph.inp rows %s %s differ from video.inps' %s %s" % (tuple(inp.shape[2:]), inp.dtype,
+                                                                         tuple(inps.shape[1:]), inps.dtype))
+    max_factors = int(graph.max_factors)
+    may_evict = bool(remove) and corr is not None
+    target_inac = weight_inac = None
+    if may_evict:
+        target_inac = _payload(op, graph.target_inac, "target_inac", m)
+        weight_inac = _payload(op, graph.weight_inac, "weight_inac", m)
+        for nm, x in (("target_inac", target_inac), ("weight_inac", weight_inac)):
+            _require(x.dtype == torch.float32 and x.shape[2:] == target.shape[2:], op,
+                     "graph.%s rows differ from the active ones" % nm)
+    pii, pjj = _proposal(op, dev, ii, jj)
+    p = int(pii.shape[0])
+    for cnt, nm in ((n, "active"), (m, "inactive"), (p, "proposed")):
+        _require(cnt <= MAX_EDGES, op, "%d %s edges exceed the supported %d" % (cnt, nm, MAX_EDGES))
+    res = dict(added=0, filtered=p, evicted=0, plan_launches=0, payload_launches=0, host_reads=0)
+    if p == 0:
+        return res
+    lib = _lib.load()
+    lists = torch.empty(3, n + p, dtype=torch.int64, device=dev)
+    inac = torch.empty(2, m + n, dtype=torch.int64, device=dev) if may_evict else None
+    info = torch.empty(AF_INFO_WORDS + 2 * n + 3 * p, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.dba_add_factors_plan(_ptr(graph.ii), _ptr(graph.jj), _ptr(graph.age), n, _ptr(graph.ii_inac),
+                                            _ptr(graph.jj_inac), m, _ptr(pii), _ptr(pjj), p, max_factors, int(may_evict),
+                                            n_frames, cams, _ptr(lists), _ptr(inac), _ptr(info), _stream(dev)),
+                   "dba_add_factors_plan")
+    stats["plan_launches"] += 1
+    host = info.cpu().tolist()   # the one host synchronisation of the call
+    stats["host_reads"] += 1
+    n_new, n_keep, n_drop, verdict, evicted = host[:5]
+    res.update(added=n_new, filtered=p - n_new, plan_launches=1, host_reads=1)
+    if n_new == 0:   # :114-115
+        return res
+    assert n_keep + n_drop == n and 0 <= n_new <= p and (evicted or n_drop == 0), "dba_add_factors_plan: inconsistent counts"
+    _require(verdict != 2, op, "a proposed stereo edge (i, i) needs the second camera's map, video.fmaps has %d" % cams)
+    _require(verdict == 0, op, "a proposed frame index lies outside the video's %d rows" % n_frames)
+    keep = host[AF_INFO_WORDS:AF_INFO_WORDS + n_keep]
+    at = AF_INFO_WORDS
+    keep_pos, drop_pos = info[at:at + n_keep], info[at + n:at + n + n_drop]
+    at += 2 * n
+    row_net, row_f1, row_f2 = info[at:at + n_new], info[at + p:at + p + n_new], info[at + 2 * p:at + 2 * p + n_new]
+    total = n_keep + n_new
+    out = dict(ii=lists[0, :total], jj=lists[1, :total], age=lists[2, :total])
+    ii_new, jj_new = lists[0, n_keep:total], lists[1, n_keep:total]
+
+    jobs = []   # (kind, src rows, dst rows, pos, count, dst_row0)
+
+    def appended(old, src_rows, kind, pos):
+        """[1, n_keep + n_new, ...]: the kept rows of `old` (none when it is None), then n_new rows of the given kind"""
+        rows = src_rows.shape[1:] if src_rows is not None else old.shape[2:]
+        dtype = src_rows.dtype if src_rows is not None else old.dtype
+        k = n_keep if old is not None else 0
+        new = torch.empty((1, k + n_new) + tuple(rows), dtype=dtype, device=dev)
+        if k:
+            jobs.append((AF_GATHER, old[0], new[0], keep_pos, k, 0))
+        jobs.append((kind, src_rows, new[0], pos, n_new, k))
+        return new
+
+    if evicted:   # :157-160
+        for nm, old, act in (("target_inac", target_inac, target), ("weight_inac", weight_inac, weight)):
+            new = old.new_empty((1, m + n_drop) + tuple(old.shape[2:]))
+            jobs.append((AF_COPY, old[0], new[0], None, m, 0))
+            jobs.append((AF_GATHER, act[0], new[0], drop_pos, n_drop, m))
+            out[nm] = new
+        out["ii_inac"], out["jj_inac"] = inac[0, :m + n_drop], inac[1, :m + n_drop]
+    out["net"] = appended(net, nets, AF_GATHER, row_net)                     # :124, :146
+    f1 = f2 = None
+    if volume:
+        out["inp"] = appended(inp, inps, AF_GATHER, row_net)                 # :134-135
+        fm_rows = fmaps.view((fmaps.shape[0] * cams,) + tuple(fmaps.shape[2:]))
+        f1 = appended(None, fm_rows, AF_GATHER, row_f1)                      # :129
+        f2 = appended(None, fm_rows, AF_GATHER, row_f2)                      # :130
+    out["target"] = appended(target, None, AF_REPROJECT, None)               # :138, :148
+    out["weight"] = appended(weight, None, AF_ZERO, None)                    # :139, :149
+
+    live = [j for j in jobs if j[4] > 0]
+    assert sum(j[0] != AF_REPROJECT for j in live) <= MAX_ADD_JOBS
+    table = (_lib.AfJob * max(len(live), 1))()
+    for k, j in enumerate(live):
+        _af_job(table, k, *j)
+    geom = _lib.AfGeometry(poses.data_ptr(), disps.data_ptr(), intr.data_ptr(), ii_new.data_ptr(), jj_new.data_ptr(),
+                           n_frames, ht, wd, 0)
+    with torch.cuda.device(dev):
+        _lib.check(lib.dba_add_factors_payload(table, len(live), ctypes.byref(geom), _stream(dev)),
+                   "dba_add_factors_payload")
+    stats["payload_launches"] += 1
+    res.update(evicted=n_drop, payload_launches=1)
+
+    if volume:   # :127-132, after rm_factors' :167-168
+        if corr is not None and evicted:
+            corr = corr[keep]   # a host list: the CorrBlock edits its slot table, no device read
+        new_corr = CorrBlock(f1, f2)
+        out["corr"] = new_corr if corr is None else corr.cat(new_corr)
+    for nm, x in out.items():
+        setattr(graph, nm, x)
+    return res
+
+
+def add_neighborhood_factors(graph, t0, t1, r=3):
+    """CovisibleGraph.add_neighborhood_factors (dbaf/covisible_graph.py:344-354): the edges (i, j) of
+    meshgrid(arange(t0, t1), arange(t0, t1)), row-major, with c < |i - j| <= r, c = 1 for a stereo video, handed to
+    add_factors.  The grid is formed on the host and uploaded in add_factors' one copy."""
+    c = 1 if graph.video.stereo else 0
+    edges = [(i, j) for i in range(int(t0), int(t1)) for j in range(int(t0), int(t1)) if c < abs(i - j) <= r]
+    return add_factors(graph, [e[0] for e in edges], [e[1] for e in edges])

@@ -676,6 +676,62 @@ int dba_move_rows(const dba_row_job *jobs_host, int n_jobs, dba_stream_t stream)
 int dba_shift_rows(void *const *bases_host, const int64_t *row_bytes_host, const int64_t *rows_host, int n_bufs,
                    int64_t ix, dba_stream_t stream);
 
+/* ---- adding edges (csrc/add_factors.hip) ----------------------------------------------------------------------------
+ * CovisibleGraph.add_factors (dbaf/covisible_graph.py:102-149) in two launches around one host read.
+ * dba_add_factors_plan: one launch, one workgroup, no atomics.  From the active lists (ii, jj, age)[n], the inactive
+ *   lists (ii_inac, jj_inac)[n_inac] and the proposal (prop_ii, prop_jj)[n_prop]:
+ *     filter   the proposals in neither list, in order, duplicates inside the proposal kept (:61-72); n_new of them
+ *     evict    when n_new > 0 && may_evict && max_factors > 0 && n + n_new > max_factors (:118-119; may_evict = `remove`
+ *              and a standing corr): mask[k] = argsort(age)[k] >= max_factors - n_new over POSITIONS k (:121-122), the
+ *              argsort stable (ties to the lower position); a negative limit drops everything
+ *     lists    [3, n + n_prop] int64 out: rows ii, jj, age; the kept edges in order, then the new ones with age 0;
+ *              n_keep + n_new entries of each row are written (:141-143, :163-165)
+ *     inac     [2, n_inac + n] int64 out, written only on eviction: the inactive lists, then the dropped edges (:157-158)
+ *     info     [DBA_AF_INFO_WORDS + 2 n + 3 n_prop] int32 out, what the host reads in one copy: n_new, n_keep, n_drop,
+ *              the verdict, 1 if the eviction ran, three spare words; then the kept positions (n slots) and the dropped
+ *              positions (n slots), position lists as dba_move_rows takes them; then n_prop slots each of the source
+ *              rows of the gathers: ii_new (nets, inps), ii_new * cams and jj_new * cams + (ii_new == jj_new) (fmaps
+ *              [n_frames, cams, ...] viewed as rows, :128-130)
+ *   verdict: 0, or DBA_AF_BAD_RANGE when a kept proposal has an index outside [0, n_frames), or DBA_AF_BAD_STEREO when
+ *   a kept (i, i) needs a second camera and cams < 2 (the reference raises IndexError at :130).  The source rows of
+ *   such an edge are written as -1, which the payload launch skips; the caller is expected to stop on a verdict.
+ *   Any of n, n_inac, n_prop > 8192 is DBA_ERR_UNSUPPORTED.
+ * dba_add_factors_payload: ONE launch that executes up to DBA_AF_MAX_JOBS row jobs
+ *     DBA_AF_COPY       dst[dst_row0 + r] = src[r]                    (the inactive store in front of what it gains)
+ *     DBA_AF_GATHER     dst[dst_row0 + r] = src[pos[r]]               (kept rows, dropped rows, nets[ii], fmaps[ii, 0] ...)
+ *     DBA_AF_ZERO       dst[dst_row0 + r] = 0                         (the new weight rows, :139)
+ *   r in [0, count), rows moved as dba_move_rows moves them (the same body and vector widths; a position outside
+ *   [0, src_rows) copies nothing), and at most one
+ *     DBA_AF_REPROJECT  dst[dst_row0 + e] = the coordinates of dba_reproject for edge (geom->ii[e], geom->jj[e]), bit for
+ *                       bit, rows of [ht, wd, 2] float32 (:138); an edge with an index outside [0, geom->n_frames) writes
+ *                       nothing
+ *   The tables are host arrays, passed to the kernel by value.  Neither call synchronises. */
+#define DBA_AF_INFO_WORDS 8
+#define DBA_AF_BAD_RANGE 1
+#define DBA_AF_BAD_STEREO 2
+#define DBA_AF_MAX_JOBS 16
+#define DBA_AF_COPY 0
+#define DBA_AF_GATHER 1
+#define DBA_AF_ZERO 2
+#define DBA_AF_REPROJECT 3
+typedef struct dba_af_job {
+  int kind, reserved;
+  dba_row_job rows; /* src unused by ZERO and REPROJECT, pos used by GATHER only */
+} dba_af_job;
+typedef struct dba_af_geometry {
+  const float *poses;         /* device [n_frames, 7] */
+  const float *disps;         /* device [n_frames, ht, wd] */
+  const float *intrinsics_b4; /* device [n_frames, 4] */
+  const int64_t *ii, *jj;     /* device: the edges of the REPROJECT job */
+  int n_frames, ht, wd, reserved;
+} dba_af_geometry;
+int dba_add_factors_plan(const int64_t *ii, const int64_t *jj, const int64_t *age, int n, const int64_t *ii_inac,
+                         const int64_t *jj_inac, int n_inac, const int64_t *prop_ii, const int64_t *prop_jj, int n_prop,
+                         int max_factors, int may_evict, int n_frames, int cams, int64_t *lists, int64_t *inac,
+                         int *info, dba_stream_t stream);
+int dba_add_factors_payload(const dba_af_job *jobs_host, int n_jobs, const dba_af_geometry *geom_host,
+                            dba_stream_t stream);
+
 /* ---- the VIO update's BA inputs (csrc/update_inputs.hip) ------------------------------------------------------------
  * What CovisibleGraph.update(use_inactive=True) computes between the update operator and video.ba
  * (dbaf/covisible_graph.py:229-230, :242-247, :311-333), and the four .item() reads of DepthVideo.ba
