@@ -6,9 +6,9 @@
 //                               appended inactive store (rm_factors, :159-160, :170-176), the gathers nets[ii], inps[ii],
 //                               fmaps[ii,0], fmaps[jj,c] (:124-134), video.reproject(ii, jj) (:138), zeros_like (:139)
 //                               and the torch.cat that follow (:135, :146-149), in one launch
-// The plan is one workgroup of 1024 lanes:
-//   - filter: a lane holds up to 8 proposals in registers; the active and the inactive list pass through LDS a tile at
-//     a time; the survivors are numbered in order by ballot + prefix sums (duplicates inside the proposal stay);
+// The plan is one workgroup of 1024 lanes (the filter and the compaction are edge_lists.h's):
+//   - filter: a lane holds up to 8 proposals in registers and strikes those in the active or the inactive list; the
+//     survivors are numbered in order (duplicates inside the proposal stay);
 //   - eviction: edge e's stable rank r(e) = #{f: age[f] < age[e]} + #{f < e: age[f] == age[e]} is argsort's inverse
 //     (ties to the lower position), so position r(e) of the mask is `e >= limit`; the mask goes to LDS and is compacted
 //     as dba_select_edges compacts its mask: both sides in the input's order;
@@ -23,6 +23,7 @@
 #include <stdint.h>
 
 #include "common.h"
+#include "edge_lists.h"
 #include "reproj.h"
 #include "row_jobs.h"
 
@@ -30,23 +31,6 @@ namespace dba {
 
 constexpr int AF_THREADS = 1024;
 constexpr int AF_PER = DBA_SEL_MAX_EDGES / AF_THREADS;  // list entries per lane
-
-// the slot of a raised flag among the workgroup's raised flags, in lane order (all lanes call it); *total = their number
-__device__ __forceinline__ int flag_slot(bool f, int *wcount, int *total) {
-  const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x >> 6;
-  const uint64_t m = __ballot(f);
-  if (lane == 0) wcount[wv] = __popcll(m);
-  __syncthreads();
-  int before = 0, tot = 0;
-  for (int w = 0; w < AF_THREADS / WAVE; w++) {
-    const int s = wcount[w];
-    if (w < wv) before += s;
-    tot += s;
-  }
-  __syncthreads();
-  *total = tot;
-  return before + __popcll(m & ((1ull << lane) - 1ull));
-}
 
 __global__ __launch_bounds__(AF_THREADS) void add_factors_plan_kernel(
     const int64_t *__restrict__ ii, const int64_t *__restrict__ jj, const int64_t *__restrict__ age, int n,
@@ -71,23 +55,8 @@ __global__ __launch_bounds__(AF_THREADS) void add_factors_plan_kernel(
     a[t] = fresh[t] ? pii[k] : 0;
     b[t] = fresh[t] ? pjj[k] : 0;
   }
-  for (int which = 0; which < 2; which++) {
-    const int64_t *ei = which ? ii_inac : ii, *ej = which ? jj_inac : jj;
-    const int ne_all = which ? m : n;
-    for (int e0 = 0; e0 < ne_all; e0 += AF_THREADS) {
-      const int ne = min(ne_all - e0, AF_THREADS);
-      __syncthreads();
-      if (tid < ne) { sx[0][tid] = ei[e0 + tid]; sx[1][tid] = ej[e0 + tid]; }
-      __syncthreads();
-#pragma unroll
-      for (int t = 0; t < AF_PER; t++) {
-        if (t >= p_tiles) break;
-        if (fresh[t])
-          for (int e = 0; e < ne; e++)
-            if (sx[0][e] == a[t] && sx[1][e] == b[t]) { fresh[t] = false; break; }
-      }
-    }
-  }
+  strike_listed<AF_THREADS>(ii, jj, n, a, b, fresh, p_tiles, sx);
+  strike_listed<AF_THREADS>(ii_inac, jj_inac, m, a, b, fresh, p_tiles, sx);
   int q_new[AF_PER];
   int n_new = 0;
 #pragma unroll
@@ -95,7 +64,7 @@ __global__ __launch_bounds__(AF_THREADS) void add_factors_plan_kernel(
     q_new[t] = 0;
     if (t >= p_tiles) continue;
     int tot;
-    q_new[t] = n_new + flag_slot(fresh[t], wcount, &tot);
+    q_new[t] = n_new + flag_slot<AF_THREADS>(fresh[t], wcount, &tot);
     n_new += tot;
   }
 
@@ -145,7 +114,7 @@ __global__ __launch_bounds__(AF_THREADS) void add_factors_plan_kernel(
       const bool in = k < n;
       const bool d = in && dflag[k] != 0;
       int tot;
-      const int qd = n_drop + flag_slot(d, wcount, &tot);
+      const int qd = n_drop + flag_slot<AF_THREADS>(d, wcount, &tot);
       if (in) {
         const int64_t i = ii[k], j = jj[k];
         if (d) {
@@ -262,26 +231,18 @@ int dba_add_factors_payload(const dba_af_job *jobs, int n_jobs, const dba_af_geo
     const dba_af_job &a = jobs[k];
     const dba_row_job &j = a.rows;
     if (a.kind < DBA_AF_COPY || a.kind > DBA_AF_REPROJECT) return DBA_ERR_ARG;
-    if (j.count < 0 || j.row_bytes < 0 || j.dst_row0 < 0 || j.src_rows < 0 || j.dst_rows < 0) return DBA_ERR_ARG;
-    if ((int64_t)j.dst_row0 + j.count > j.dst_rows) return DBA_ERR_ARG;
     if (a.kind == DBA_AF_REPROJECT) {
-      if (reproject) return DBA_ERR_ARG;  // one per call
+      if (!row_range_ok(j) || reproject) return DBA_ERR_ARG;  // one per call
       reproject = &a;
       continue;
     }
-    if (a.kind == DBA_AF_COPY && (j.pos || j.count > j.src_rows)) return DBA_ERR_ARG;
-    if (a.kind == DBA_AF_GATHER && j.count > 0 && !j.pos) return DBA_ERR_ARG;
-    if (j.count == 0 || j.row_bytes == 0) continue;
-    if (!j.dst || (a.kind != DBA_AF_ZERO && !j.src)) return DBA_ERR_ARG;
-    const char *s0 = a.kind == DBA_AF_ZERO ? nullptr : (const char *)j.src;
-    if (s0) {
-      const char *s1 = s0 + (int64_t)j.src_rows * j.row_bytes;
-      const char *d0 = (const char *)j.dst + (int64_t)j.dst_row0 * j.row_bytes, *d1 = d0 + (int64_t)j.count * j.row_bytes;
-      if (s0 < d1 && d0 < s1) return DBA_ERR_ARG;  // the rows read and the rows written overlap
-    }
+    const bool reads = a.kind != DBA_AF_ZERO;
+    const int live = check_row_job(j, reads, a.kind == DBA_AF_COPY ? POS_FORBIDDEN : POS_REQUIRED);
+    if (live < 0) return live;
+    if (!live) continue;
     if (t.n == DBA_AF_MAX_JOBS) return DBA_ERR_ARG;
-    if (!push_job(t, wgs, s0, (char *)j.dst, a.kind == DBA_AF_GATHER ? j.pos : nullptr, j.row_bytes, j.count, j.dst_row0,
-                  j.src_rows))
+    if (!push_job(t, wgs, reads ? (const char *)j.src : nullptr, (char *)j.dst, a.kind == DBA_AF_GATHER ? j.pos : nullptr,
+                  j.row_bytes, j.count, j.dst_row0, j.src_rows))
       return DBA_ERR_UNSUPPORTED;
   }
   rp.wg_start = (unsigned)wgs;

@@ -6,14 +6,14 @@
 //                        store) that one such call performs, in one launch
 //   dba_shift_rows    <- rm_keyframe's buf[ix] = buf[ix+1] over the video buffers (covisible_graph.py:185-195)
 // The reference runs these as boolean-index statements, each a nonzero with a host synchronisation of its own.  Here:
-//   - selection: one workgroup of 1024 lanes walks the edge list a tile at a time.  Each wave ballots its drop flags;
-//     a lane's slot among the dropped is the dropped count of the tiles before, of the waves before (LDS) and of the
-//     lanes before (popcount of the ballot below the lane); its slot among the kept is its position minus that.  Both
-//     sides therefore come out in the input's order, which is the order boolean indexing gives.  No atomics.
+//   - selection: one workgroup of 1024 lanes walks the edge list a tile at a time.  A lane's slot among the dropped is
+//     the dropped count of the tiles before plus its slot in the tile (flag_slot, edge_lists.h); its slot among the kept
+//     is its position minus that.  Both sides therefore come out in the input's order, which is the order boolean
+//     indexing gives.  No atomics.
 //   - row mover: a job table passed by value in the kernel arguments; the grid is the concatenation of every job's
 //     (row, chunk) pairs, a chunk being 1024 elements of the job's vector width (16 KB at 16 bytes), four loads in
-//     flight per lane before the first store.  Pure streaming: no LDS, plain vector stores.  (The table and the
-//     copy body are in row_jobs.h, which add_factors.hip shares.)
+//     flight per lane before the first store.  Pure streaming: no LDS, plain vector stores.  (The table, the
+//     copy body and the check of a job are in row_jobs.h, which add_factors.hip shares.)
 //   - row shift: the same body over a table of one-row jobs.
 // Nothing synchronises the host; the selection leaves its counts and position lists in one small buffer.
 #include <hip/hip_runtime.h>
@@ -21,6 +21,7 @@
 #include <stdint.h>
 
 #include "common.h"
+#include "edge_lists.h"
 #include "row_jobs.h"
 
 namespace dba {
@@ -33,7 +34,7 @@ __global__ __launch_bounds__(SEL_THREADS) void select_edges_kernel(
     const int64_t *__restrict__ pre_jj, int n_pre, int64_t *__restrict__ keep, int64_t *__restrict__ drop,
     int *__restrict__ sel) {
   __shared__ int wdrop[SEL_THREADS / WAVE];
-  const int tid = threadIdx.x, lane = tid & (WAVE - 1), wv = tid >> 6;
+  const int tid = threadIdx.x;
   int64_t *kii = keep, *kjj = keep + n, *kage = keep + 2 * (int64_t)n;
   int64_t *dii = drop, *djj = drop + (n_pre + n);
   int *keep_pos = sel + 2, *drop_pos = sel + 2 + n;
@@ -68,17 +69,8 @@ __global__ __launch_bounds__(SEL_THREADS) void select_edges_kernel(
           break;
       }
     }
-    const uint64_t m = __ballot(d);
-    if (lane == 0) wdrop[wv] = __popcll(m);
-    __syncthreads();
-    int before = 0, total = 0;
-    for (int w = 0; w < SEL_THREADS / WAVE; w++) {
-      const int s = wdrop[w];
-      if (w < wv) before += s;
-      total += s;
-    }
-    __syncthreads();
-    const int q_drop = dropped + before + __popcll(m & ((1ull << lane) - 1ull));
+    int total;
+    const int q_drop = dropped + flag_slot<SEL_THREADS>(d, wdrop, &total);
     if (in) {
       if (d) {
         dii[n_pre + q_drop] = i;
@@ -131,15 +123,10 @@ int dba_move_rows(const dba_row_job *jobs, int n_jobs, dba_stream_t stream) {
   uint64_t wgs = 0;
   for (int k = 0; k < n_jobs; k++) {
     const dba_row_job &j = jobs[k];
-    if (j.count < 0 || j.row_bytes < 0 || j.dst_row0 < 0 || j.src_rows < 0 || j.dst_rows < 0) return DBA_ERR_ARG;
-    if ((int64_t)j.dst_row0 + j.count > j.dst_rows) return DBA_ERR_ARG;
-    if (!j.pos && j.count > j.src_rows) return DBA_ERR_ARG;
-    if (j.count == 0 || j.row_bytes == 0) continue;
-    if (!j.src || !j.dst) return DBA_ERR_ARG;
-    const char *s0 = (const char *)j.src, *s1 = s0 + (int64_t)j.src_rows * j.row_bytes;
-    const char *d0 = (const char *)j.dst + (int64_t)j.dst_row0 * j.row_bytes, *d1 = d0 + (int64_t)j.count * j.row_bytes;
-    if (s0 < d1 && d0 < s1) return DBA_ERR_ARG;  // the rows read and the rows written overlap
-    if (!push_job(t, wgs, s0, (char *)j.dst, j.pos, j.row_bytes, j.count, j.dst_row0, j.src_rows))
+    const int live = check_row_job(j, true, POS_OPTIONAL);
+    if (live < 0) return live;
+    if (!live) continue;
+    if (!push_job(t, wgs, (const char *)j.src, (char *)j.dst, j.pos, j.row_bytes, j.count, j.dst_row0, j.src_rows))
       return DBA_ERR_UNSUPPORTED;
   }
   if (t.n == 0) return DBA_OK;

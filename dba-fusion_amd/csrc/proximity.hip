@@ -15,8 +15,8 @@
 //     (distance, index), which is torch.argsort's order with ties broken by the lower index.  Wave 0 then walks the
 //     sorted list 64 candidates at a time: a ballot finds the first one whose CURRENT distance is still takeable, it is
 //     appended and its neighbourhood suppressed, and the walk resumes after it;
-//   - the repeated-edge filter: one workgroup, an order-preserving compaction (block scan) of the proposals that are
-//     not in the existing list.
+//   - the repeated-edge filter: one workgroup, one proposal per lane a tile at a time, through the filter and the
+//     order-preserving compaction of edge_lists.h.
 // No atomics anywhere: every result is bit-identical run to run.  Nothing synchronises the host; each call writes its
 // edge count to a caller-provided device word.
 #include <hip/hip_runtime.h>
@@ -26,6 +26,7 @@
 #include <stdint.h>
 
 #include "common.h"
+#include "edge_lists.h"
 #include "frame_distance.h"
 
 namespace dba {
@@ -275,21 +276,13 @@ __global__ __launch_bounds__(PROX_THREADS) void filter_repeated_edges_kernel(
   int base = 0;
   for (int start = 0; start < n; start += PROX_THREADS) {
     const int p = start + threadIdx.x;
-    int64_t a = 0, b = 0;
-    bool keep = p < n;
-    if (keep) { a = ii[p]; b = jj[p]; }
-    for (int e0 = 0; e0 < n_ex; e0 += PROX_THREADS) {
-      const int ne = min(n_ex - e0, PROX_THREADS);
-      __syncthreads();
-      if ((int)threadIdx.x < ne) { sx[0][threadIdx.x] = ex_ii[e0 + threadIdx.x]; sx[1][threadIdx.x] = ex_jj[e0 + threadIdx.x]; }
-      __syncthreads();
-      if (keep)
-        for (int e = 0; e < ne; e++)
-          if (sx[0][e] == a && sx[1][e] == b) { keep = false; break; }
-    }
+    int64_t a[1] = {0}, b[1] = {0};
+    bool keep[1] = {p < n};
+    if (keep[0]) { a[0] = ii[p]; b[0] = jj[p]; }
+    strike_listed<PROX_THREADS>(ex_ii, ex_jj, n_ex, a, b, keep, 1, sx);
     int tot;
-    const int off = block_exclusive_scan(keep ? 1 : 0, wsum, &tot);
-    if (keep) { out_ii[base + off] = a; out_jj[base + off] = b; }
+    const int off = flag_slot<PROX_THREADS>(keep[0], wsum, &tot);
+    if (keep[0]) { out_ii[base + off] = a[0]; out_jj[base + off] = b[0]; }
     base += tot;
   }
   if (threadIdx.x == 0) *count = base;

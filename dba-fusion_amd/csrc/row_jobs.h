@@ -8,6 +8,8 @@
 
 #include <stdint.h>
 
+#include "../../include/dba_hip.h"
+
 namespace dba {
 
 constexpr int MOVE_THREADS = 256;
@@ -98,6 +100,34 @@ __device__ __forceinline__ void run_row_jobs(const RowTable<N> &t) {
 }
 
 // ---- host side: filling a table ------------------------------------------------------------------------------------
+
+// the checks every kind of job passes: no negative size, and the rows written fit dst
+inline bool row_range_ok(const dba_row_job &j) {
+  if (j.count < 0 || j.row_bytes < 0 || j.dst_row0 < 0 || j.src_rows < 0 || j.dst_rows < 0) return false;
+  return (int64_t)j.dst_row0 + j.count <= j.dst_rows;
+}
+
+enum PosRule { POS_FORBIDDEN, POS_OPTIONAL, POS_REQUIRED };
+
+// The one validation of a dba_row_job: DBA_ERR_ARG, 0 for a job that moves nothing (it is left out of the table) or 1
+// for a job to push.  reads: the rows come from j.src, and `pos` says whether the job may, must or must not name them
+// through j.pos; a job that reads nothing (its rows are zeroed) is asked for neither src nor pos.
+inline int check_row_job(const dba_row_job &j, bool reads, PosRule pos) {
+  if (!row_range_ok(j)) return DBA_ERR_ARG;
+  if (reads) {
+    if (pos == POS_FORBIDDEN && j.pos) return DBA_ERR_ARG;
+    if (pos == POS_REQUIRED && j.count > 0 && !j.pos) return DBA_ERR_ARG;
+    if (!j.pos && j.count > j.src_rows) return DBA_ERR_ARG;
+  }
+  if (j.count == 0 || j.row_bytes == 0) return 0;
+  if (!j.dst || (reads && !j.src)) return DBA_ERR_ARG;
+  if (reads) {
+    const char *s0 = (const char *)j.src, *s1 = s0 + (int64_t)j.src_rows * j.row_bytes;
+    const char *d0 = (const char *)j.dst + (int64_t)j.dst_row0 * j.row_bytes, *d1 = d0 + (int64_t)j.count * j.row_bytes;
+    if (s0 < d1 && d0 < s1) return DBA_ERR_ARG;  // the rows read and the rows written overlap
+  }
+  return 1;
+}
 
 // the widest of 16 / 8 / 4 / 2 / 1 bytes that divides the row size and both base addresses
 inline int vector_width(const void *s, const void *d, int64_t row_bytes) {

@@ -1,7 +1,7 @@
 // The statements of CovisibleGraph.update() between the update operator and video.ba (dbaf/covisible_graph.py:229-230,
 // :242-247, :311-333, use_inactive=True), gfx950, two launches:
 //   edge pass     one workgroup of 1024 lanes, no atomics.  t0 = max(1, min(ii) + 1) (:230); the inactive edges inside
-//                 the window compacted in list order (wave ballots + prefix sums, :243) and the active list appended
+//                 the window compacted in list order (flag_slot, edge_lists.h, :243) and the active list appended
 //                 (:244-245); min / max of the concatenated lists (:327-328 and depth_video.py:327-348); torch.unique of
 //                 the concatenated ii through a presence table in LDS (:330); one byte of flags per output edge: bit 0
 //                 short baseline (:317-321), bit 1 ii == max(ii) (:327), bit 2 jj == max(jj) (:328); a result block of
@@ -22,6 +22,7 @@
 #include <mutex>
 
 #include "common.h"
+#include "edge_lists.h"
 
 namespace dba {
 
@@ -94,7 +95,7 @@ __global__ __launch_bounds__(UI_THREADS) void update_inputs_edge_kernel(
   __shared__ int wcount[UI_WAVES];
   __shared__ int red[UI_WAVES];
   __shared__ unsigned char present[DBA_UI_MAX_FRAMES];
-  const int tid = threadIdx.x, lane = tid & (WAVE - 1), wv = tid >> 6;
+  const int tid = threadIdx.x;
   present[tid] = 0;  // (DBA_UI_MAX_FRAMES == UI_THREADS)
 
   // :230, over the ACTIVE list alone
@@ -121,19 +122,9 @@ __global__ __launch_bounds__(UI_THREADS) void update_inputs_edge_kernel(
       j = jj_inac[p];
       k = i >= oldest && j >= oldest;
     }
-    const uint64_t m = __ballot(k);
-    if (lane == 0) wcount[wv] = __popcll(m);
-    __syncthreads();
-    int before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < UI_WAVES; w++) {
-      const int s = wcount[w];
-      if (w < wv) before += s;
-      total += s;
-    }
-    __syncthreads();
+    int total;
+    const int q = kept + flag_slot<UI_THREADS>(k, wcount, &total);
     if (k) {
-      const int q = kept + before + __popcll(m & ((1ull << lane) - 1ull));
       sel[q] = p;
       ii_out[q] = i;
       jj_out[q] = j;
@@ -163,21 +154,9 @@ __global__ __launch_bounds__(UI_THREADS) void update_inputs_edge_kernel(
 
   // :330, torch.unique(ii): the frames present, ascending
   int n_kx;
-  {
-    const bool k = present[tid] != 0;
-    const uint64_t m = __ballot(k);
-    if (lane == 0) wcount[wv] = __popcll(m);
-    __syncthreads();
-    int before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < UI_WAVES; w++) {
-      const int s = wcount[w];
-      if (w < wv) before += s;
-      total += s;
-    }
-    if (k) kx[before + __popcll(m & ((1ull << lane) - 1ull))] = tid;
-    n_kx = total;
-  }
+  const bool seen = present[tid] != 0;
+  const int q_kx = flag_slot<UI_THREADS>(seen, wcount, &n_kx);
+  if (seen) kx[q_kx] = tid;
 
   // :317-321, :327-328
   for (int e = tid; e < N; e += UI_THREADS) {

@@ -6,6 +6,8 @@ shared object is missing or a call fails, the product path raises -- it never co
 import ctypes
 import os
 
+import torch
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DBA_HIP_LIB") or os.path.join(os.path.dirname(_HERE), "lib", "libdba_hip.so")
 
@@ -189,3 +191,27 @@ def check(rc, what):
         msg = _ERR.get(rc, str(rc))
         detail = load().dba_last_error().decode() if rc == -3 else ""
         raise RuntimeError("dba_hip: %s failed with %s %s" % (what, msg, detail))
+
+
+# ---- what every ctypes caller of the edge-management entry points needs (factors, proximity, update_inputs) ----------
+
+def ptr(x):
+    """the tensor's address as a void*; a null pointer for None and for an empty tensor"""
+    return ctypes.c_void_p(x.data_ptr()) if x is not None and x.numel() else None
+
+
+def require(cond, op, msg):
+    if not cond:
+        raise ValueError("%s (MI355X): %s" % (op, msg))
+
+
+def stream(dev):
+    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def check_edge_list(op, dev, x, nm):
+    """x must be a contiguous 1-D int64 device tensor, on `dev` unless that is None"""
+    require(isinstance(x, torch.Tensor) and x.is_cuda and (dev is None or x.device == dev), op,
+            "%s must be a HIP device tensor%s; no CPU path" % (nm, "" if dev is None else " on %s" % dev))
+    require(x.dtype == torch.int64 and x.dim() == 1 and x.is_contiguous(), op,
+            "%s must be a contiguous 1-D int64 tensor" % nm)

@@ -27,10 +27,12 @@ new target rows (reprojected in the kernel) and the zeroed weight rows.  The vol
 `stats` counts the launches and host reads of this module since import (as CorrBlock.stats does for the pyramid).
 """
 import ctypes
+import math
 
 import torch
 
 from . import _lib
+from ._lib import ptr as _ptr, require as _require, stream as _stream, check_edge_list as _check_list
 
 MAX_EDGES = 8192       # per selection call
 MAX_ROW_JOBS = 8       # per move_rows call
@@ -42,26 +44,6 @@ AF_COPY, AF_GATHER, AF_ZERO, AF_REPROJECT = range(4)
 AF_INFO_WORDS = 8
 
 stats = dict(select_launches=0, mover_launches=0, shift_launches=0, host_reads=0, plan_launches=0, payload_launches=0)
-
-
-def _ptr(x):
-    return ctypes.c_void_p(x.data_ptr()) if x is not None else None
-
-
-def _require(cond, op, msg):
-    if not cond:
-        raise ValueError("%s (MI355X): %s" % (op, msg))
-
-
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
-def _check_list(op, dev, x, nm):
-    _require(isinstance(x, torch.Tensor) and x.is_cuda and (dev is None or x.device == dev), op,
-             "%s must be a HIP device tensor%s; no CPU path" % (nm, "" if dev is None else " on %s" % dev))
-    _require(x.dtype == torch.int64 and x.dim() == 1 and x.is_contiguous(), op,
-             "%s must be a contiguous 1-D int64 tensor" % nm)
 
 
 # ---- selection ------------------------------------------------------------------------------------------------------
@@ -190,10 +172,16 @@ def _rows(op, x, nm, dev):
     _require(isinstance(x, torch.Tensor) and x.is_cuda and (dev is None or x.device == dev), op,
              "%s must be a HIP device tensor%s; no CPU path" % (nm, "" if dev is None else " on %s" % dev))
     _require(x.dim() >= 1 and x.is_contiguous(), op, "%s must be contiguous with its rows along dim 0" % nm)
-    row_bytes = x.element_size()
-    for d in x.shape[1:]:
-        row_bytes *= int(d)
-    return int(x.shape[0]), row_bytes
+    return int(x.shape[0]), x.element_size() * math.prod(x.shape[1:])
+
+
+def _fill_row_job(j, src, dst, pos, count, dst_row0):
+    """fills the RowJob j; src / dst are [rows, ...] tensors of one row shape (src None where the rows are produced),
+    pos an int32 device tensor or None"""
+    j.src = src.data_ptr() if src is not None else None
+    j.dst, j.pos = dst.data_ptr(), (pos.data_ptr() if pos is not None else None)
+    j.row_bytes, j.count, j.dst_row0 = dst.element_size() * math.prod(dst.shape[1:]), int(count), int(dst_row0)
+    j.src_rows, j.dst_rows = (int(src.shape[0]) if src is not None else 0), int(dst.shape[0])
 
 
 def move_rows(jobs):
@@ -229,9 +217,7 @@ def move_rows(jobs):
             _require(not (s0 < d0 + count * rb and d0 < s0 + src_rows * rb), op,
                      "job %d: the rows read and the rows written overlap" % k)
             live += 1
-        j = table[k]
-        j.src, j.dst, j.pos = src.data_ptr(), dst.data_ptr(), (pos.data_ptr() if pos is not None else None)
-        j.row_bytes, j.count, j.dst_row0, j.src_rows, j.dst_rows = rb, count, dst_row0, src_rows, dst_rows
+        _fill_row_job(table[k], src, dst, pos, count, dst_row0)
     if not live:
         return 0
     with torch.cuda.device(dev):
@@ -279,6 +265,17 @@ def _kept_rows(jobs, x, s):
     return new
 
 
+def _store_dropped(out, stores, m, drop_pos, n_drop):
+    """:159-160 for every (name, old store, active tensor) of `stores`: out[name] = a new store of m + n_drop rows;
+    returns the row jobs that fill it, the old store's m rows and then the active rows at drop_pos"""
+    jobs = []
+    for nm, old, act in stores:
+        new = old.new_empty((1, m + n_drop) + tuple(old.shape[2:]))
+        jobs += [(old[0], new[0], None, m, 0), (act[0], new[0], drop_pos, n_drop, m)]
+        out[nm] = new
+    return jobs
+
+
 def _drop_active(op, graph, s, store, jobs):
     """rm_factors' statements after the mask (:156-176) for the selection `s` of the active list; appends the payload
     jobs to `jobs` and returns the attribute assignments to make once they are enqueued"""
@@ -286,13 +283,12 @@ def _drop_active(op, graph, s, store, jobs):
     target, weight = _payload(op, graph.target, "target", s.n), _payload(op, graph.weight, "weight", s.n)
     if store:   # :157-161
         m = int(graph.ii_inac.shape[0])
+        stores = []
         for nm, x in (("target_inac", target), ("weight_inac", weight)):
             old = _payload(op, getattr(graph, nm), nm, m)
             _require(old.dtype == x.dtype and old.shape[2:] == x.shape[2:], op, "graph.%s rows differ from the active ones" % nm)
-            new = old.new_empty((1, m + s.n_drop) + tuple(old.shape[2:]))
-            jobs.append((old[0], new[0], None, m, 0))
-            jobs.append((x[0], new[0], s.drop_pos, s.n_drop, m))
-            out[nm] = new
+            stores.append((nm, old, x))
+        jobs += _store_dropped(out, stores, m, s.drop_pos, s.n_drop)
         out["ii_inac"], out["jj_inac"] = s.drop_ii, s.drop_jj
     out["ii"], out["jj"], out["age"] = s.ii, s.jj, s.age   # :163-165
     for nm in ("net", "inp"):                              # :170-174
@@ -417,16 +413,8 @@ def _video_rows(op, x, nm, dev, dtype=None):
 
 def _af_job(table, k, kind, src, dst, pos, count, dst_row0):
     """fills table[k]; src / dst are [rows, ...] views, pos an int32 device tensor or None"""
-    j = table[k]
-    j.kind = kind
-    r = j.rows
-    row_bytes = dst.element_size()
-    for d in dst.shape[1:]:
-        row_bytes *= int(d)
-    r.src = src.data_ptr() if src is not None else None
-    r.dst, r.pos = dst.data_ptr(), (pos.data_ptr() if pos is not None else None)
-    r.row_bytes, r.count, r.dst_row0 = row_bytes, int(count), int(dst_row0)
-    r.src_rows, r.dst_rows = (int(src.shape[0]) if src is not None else 0), int(dst.shape[0])
+    table[k].kind = kind
+    _fill_row_job(table[k].rows, src, dst, pos, count, dst_row0)
 
 
 def add_factors(graph, ii, jj, remove=False):
@@ -554,11 +542,8 @@ def add_factors(graph, ii, jj, remove=False):
         return new
 
     if evicted:   # :157-160
-        for nm, old, act in (("target_inac", target_inac, target), ("weight_inac", weight_inac, weight)):
-            new = old.new_empty((1, m + n_drop) + tuple(old.shape[2:]))
-            jobs.append((AF_COPY, old[0], new[0], None, m, 0))
-            jobs.append((AF_GATHER, act[0], new[0], drop_pos, n_drop, m))
-            out[nm] = new
+        stores = (("target_inac", target_inac, target), ("weight_inac", weight_inac, weight))
+        jobs += [(AF_COPY if j[2] is None else AF_GATHER,) + j for j in _store_dropped(out, stores, m, drop_pos, n_drop)]
         out["ii_inac"], out["jj_inac"] = inac[0, :m + n_drop], inac[1, :m + n_drop]
     out["net"] = appended(net, nets, AF_GATHER, row_net)                     # :124, :146
     f1 = f2 = None

@@ -17,22 +17,10 @@ import ctypes
 import torch
 
 from . import _lib
+from ._lib import ptr as _ptr, require as _require, stream as _stream
 
 MAX_CANDIDATES = 8192   # (t - t0) * (t - t1) + skip extras per selection call
 MAX_SKIP = 16
-
-
-def _ptr(x):
-    return ctypes.c_void_p(x.data_ptr()) if x is not None else None
-
-
-def _require(cond, op, msg):
-    if not cond:
-        raise ValueError("%s (MI355X): %s" % (op, msg))
-
-
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def _check_geometry(op, poses, disps, intrinsics):
@@ -51,10 +39,7 @@ def _check_geometry(op, poses, disps, intrinsics):
 
 def _check_edges(op, dev, *pairs):
     for x, nm in pairs:
-        _require(isinstance(x, torch.Tensor) and x.is_cuda and x.device == dev, op,
-                 "%s must be a HIP device tensor on %s; no CPU path" % (nm, dev))
-        _require(x.dtype == torch.int64 and x.dim() == 1 and x.is_contiguous(), op,
-                 "%s must be a contiguous 1-D int64 tensor" % nm)
+        _lib.check_edge_list(op, dev, x, nm)
 
 
 # ---- distances ------------------------------------------------------------------------------------------------------

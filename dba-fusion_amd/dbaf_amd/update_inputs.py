@@ -39,6 +39,7 @@ import weakref
 import torch
 
 from . import _lib
+from ._lib import ptr as _ptr, require as _require, stream as _stream
 
 MAX_EDGES = 8192     # per list, the limit of dbaf_amd.factors
 MAX_FRAMES = 1024    # rows of video.poses
@@ -48,19 +49,6 @@ stats = dict(edge_launches=0, payload_launches=0, host_reads=0)
 
 _CACHE = []          # the edge sets whose counts are known, newest last
 _CACHE_MAX = 8
-
-
-def _ptr(x):
-    return ctypes.c_void_p(x.data_ptr()) if x is not None and x.numel() else None
-
-
-def _require(cond, op, msg):
-    if not cond:
-        raise ValueError("%s (MI355X): %s" % (op, msg))
-
-
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def _dev_tensor(op, x, nm, dev, dtype):

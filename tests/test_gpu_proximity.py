@@ -259,7 +259,7 @@ def test_recorded_states_distances_and_edges(golden):
 
 def test_filter_edges_equals_the_model():
     rng = np.random.default_rng(13)
-    for n, n_ex in ((0, 5), (7, 0), (40, 30), (1500, 1200), (3000, 40)):
+    for n, n_ex in ((0, 5), (7, 0), (40, 30), (1500, 1200), (3000, 40), (1023, 1024), (1024, 1025), (1025, 1023)):
         ii = rng.integers(0, 20, n)
         jj = rng.integers(0, 20, n)
         ex_ii = rng.integers(0, 20, n_ex)

@@ -19,6 +19,7 @@ import pytest
 import torch
 
 import update_inputs_model as um
+from update_inputs_model import FAR_THRESHOLD, MASK_THRESHOLD, random_state
 from dbaf_amd import _lib
 from dbaf_amd import update_inputs as ux
 from lietorch import SE3
@@ -134,39 +135,6 @@ def test_fixture_states_against_torch_on_the_device(name):
     assert_same_outputs(ux.ba_inputs(g, t0=par["t0"], EP=par["EP"]), torch_reference(g, t0=par["t0"], EP=par["EP"]), name)
 
 
-MASK_THRESHOLD, FAR_THRESHOLD = 0.2, 0.3
-
-
-def random_state(window, n_act, n_inac, h, w, seed, T=60, B=64):
-    """a VIO-shaped state: banded active edges among the last `window` of T keyframes, banded inactive edges among the 22
-    frames around the oldest active one, a camera path of short (0.03) and long (0.6) steps with small random rotations.  Redrawn
-    until no baseline norm lies within 1e-4 (relative) of the threshold (the caller asserts that) and the active edges hold
-    short and long baselines."""
-    act = [(i, j) for i in range(T - window, T) for j in range(T - window, T) if 0 < abs(i - j) <= 4][-n_act:]
-    lo = min(i for i, _ in act)
-    inac = [(i, j) for i in range(lo - 20, lo + 2) for j in range(lo - 20, lo + 2) if 0 < abs(i - j) <= 4][-n_inac:]
-    assert len(act) == n_act and len(inac) == n_inac, (len(act), len(inac))
-    e = lambda lst, c: np.array([x[c] for x in lst], np.int64)  # noqa: E731
-    for attempt in range(20):
-        r = np.random.default_rng(1000 * seed + attempt)
-        step = np.where(r.random(B) < 0.4, 0.03, 0.6)[:, None] * r.normal(size=(B, 3)) / np.sqrt(3.0)
-        q = np.concatenate([0.01 * r.normal(size=(B, 3)), np.ones((B, 1))], 1)
-        poses = np.concatenate([np.cumsum(step, 0), q / np.linalg.norm(q, axis=1, keepdims=True)], 1).astype(np.float32)
-        weight = lambda n: np.where(r.random((1, n, h, w, 2)) < 0.1, 0.0, r.random((1, n, h, w, 2))).astype(np.float32)  # noqa: E731
-        st = dict(ii=e(act, 0), jj=e(act, 1), ii_inac=e(inac, 0), jj_inac=e(inac, 1),
-                  target=r.normal(size=(1, n_act, h, w, 2)).astype(np.float32) * 20, weight=weight(n_act),
-                  target_inac=r.normal(size=(1, n_inac, h, w, 2)).astype(np.float32) * 20, weight_inac=weight(n_inac),
-                  damping=(1e-6 + 1e-3 * r.random((B, h, w))).astype(np.float32), poses=poses,
-                  disps=(0.05 + 1.45 * r.random((B, h, w))).astype(np.float32))
-        ii_all, jj_all = np.concatenate([st["ii_inac"], st["ii"]]), np.concatenate([st["jj_inac"], st["jj"]])
-        norm = um.baseline_norm(poses, ii_all, jj_all)
-        short = norm < np.float32(MASK_THRESHOLD)
-        if (np.abs(norm - np.float32(MASK_THRESHOLD)) > 1e-4 * MASK_THRESHOLD).all() and short[-n_act:].any() \
-                and not short[-n_act:].all():
-            return st
-    raise AssertionError("no state with the margin and both kinds of baseline in 20 draws")
-
-
 #          window, active, inactive, ht, wd
 SHAPES = [(25, 96, 150, 64, 64), (32, 122, 150, 28, 107), (10, 54, 150, 48, 64), (12, 48, 150, 55, 55), (12, 48, 150, 64, 64)]
 
@@ -187,6 +155,24 @@ def test_random_states_against_torch_on_the_device(shape, seed, t0):
     assert_same_outputs(got, torch_reference(g, t0=par["t0"], EP=par["EP"]), (shape, seed))
     for k in ("ii", "jj", "target", "damping"):
         same_bytes(got[("target", "weight", "damping", "ii", "jj").index(k)], model[k], (shape, seed, k, "model"))
+
+
+def test_inactive_list_longer_than_one_tile_against_torch_on_the_device():
+    """1100 inactive edges: the edge pass compacts them in two tiles of 1024 lanes, with selected edges in both"""
+    st = um.multi_tile_state()
+    n_inac = len(st["ii_inac"])
+    par = dict(inac_range=3, far_threshold=FAR_THRESHOLD, mask_threshold=MASK_THRESHOLD, imu_enabled=True, t0=None, EP=1e-7)
+    model = um.assemble(st, **par)
+    sel = um.selected_positions(st, par["inac_range"])
+    assert n_inac == 1100 and 0 < model["n_sel"] == len(sel) < n_inac
+    assert (sel < 1024).any() and (sel >= 1024).any()                                            # both tiles select
+    assert (np.abs(model["norm"] - np.float32(MASK_THRESHOLD)) > 1e-4 * MASK_THRESHOLD).all()   # the margin
+    assert model["short"].any() and not model["short"].all() and model["divisions"].max() >= 2
+    g = to_graph(st, par)
+    got = ux.ba_inputs(g, EP=par["EP"])
+    assert_same_outputs(got, torch_reference(g, EP=par["EP"]), "multi-tile")
+    for k in ("ii", "jj", "target", "damping"):
+        same_bytes(got[("target", "weight", "damping", "ii", "jj").index(k)], model[k], ("multi-tile", k, "model"))
 
 
 def test_rules_off_and_no_inactive_edges():

@@ -85,3 +85,19 @@ def test_reciprocal_form_stays_within_the_derived_bound(name):
     assert np.array_equal(wa[d == 0], wb[d == 0])
     assert (np.abs(wa - wb) <= d * 2.0 ** -22 * np.abs(wa)).all()
     assert (wa != wb).any()   # the two forms do differ: the device test's allowance is not idle
+
+
+def test_multi_tile_state_selects_on_both_sides_of_the_first_tile():
+    """the 1100-edge inactive list the device test runs: the model alone says it is what that test needs"""
+    st = um.multi_tile_state()
+    par = dict(inac_range=3, far_threshold=um.FAR_THRESHOLD, mask_threshold=um.MASK_THRESHOLD, imu_enabled=True, t0=None, EP=1e-7)
+    got = um.assemble(st, **par)
+    sel = um.selected_positions(st, par["inac_range"])
+    n_inac = len(st["ii_inac"])
+    assert n_inac == 1100 and st["target_inac"].shape == (1, 1100, 8, 8, 2) and len(st["ii"]) == 48
+    assert 0 < got["n_sel"] == len(sel) < n_inac
+    assert (sel < 1024).any() and (sel >= 1024).any()
+    assert ((sel >= 1024 - 64) & (sel < 1024)).any() and ((sel >= 1024) & (sel < 1024 + 64)).any()   # the waves at the boundary
+    _same(got["ii"][:len(sel)], st["ii_inac"][sel], "the selected edges, in list order")
+    assert (np.abs(got["norm"] - np.float32(um.MASK_THRESHOLD)) > 1e-4 * um.MASK_THRESHOLD).all()
+    assert got["short"].any() and not got["short"].all() and got["divisions"].max() >= 2

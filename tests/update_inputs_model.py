@@ -71,6 +71,60 @@ def assemble(st, inac_range, far_threshold, mask_threshold, imu_enabled, t0=None
                 divisions=tr(ndiv), short=short, norm=norm)
 
 
+MASK_THRESHOLD, FAR_THRESHOLD = 0.2, 0.3
+
+
+def random_state(window, n_act, n_inac, h, w, seed, T=60, B=64):
+    """a VIO-shaped state: banded active edges among the last `window` of T keyframes, banded inactive edges among the 22
+    frames around the oldest active one, a camera path of short (0.03) and long (0.6) steps with small random rotations.  Redrawn
+    until no baseline norm lies within 1e-4 (relative) of the threshold (the caller asserts that) and the active edges hold
+    short and long baselines."""
+    act = [(i, j) for i in range(T - window, T) for j in range(T - window, T) if 0 < abs(i - j) <= 4][-n_act:]
+    lo = min(i for i, _ in act)
+    inac = [(i, j) for i in range(lo - 20, lo + 2) for j in range(lo - 20, lo + 2) if 0 < abs(i - j) <= 4][-n_inac:]
+    assert len(act) == n_act and len(inac) == n_inac, (len(act), len(inac))
+    e = lambda lst, c: np.array([x[c] for x in lst], np.int64)  # noqa: E731
+    for attempt in range(20):
+        r = np.random.default_rng(1000 * seed + attempt)
+        step = np.where(r.random(B) < 0.4, 0.03, 0.6)[:, None] * r.normal(size=(B, 3)) / np.sqrt(3.0)
+        q = np.concatenate([0.01 * r.normal(size=(B, 3)), np.ones((B, 1))], 1)
+        poses = np.concatenate([np.cumsum(step, 0), q / np.linalg.norm(q, axis=1, keepdims=True)], 1).astype(np.float32)
+        weight = lambda n: np.where(r.random((1, n, h, w, 2)) < 0.1, 0.0, r.random((1, n, h, w, 2))).astype(np.float32)  # noqa: E731
+        st = dict(ii=e(act, 0), jj=e(act, 1), ii_inac=e(inac, 0), jj_inac=e(inac, 1),
+                  target=r.normal(size=(1, n_act, h, w, 2)).astype(np.float32) * 20, weight=weight(n_act),
+                  target_inac=r.normal(size=(1, n_inac, h, w, 2)).astype(np.float32) * 20, weight_inac=weight(n_inac),
+                  damping=(1e-6 + 1e-3 * r.random((B, h, w))).astype(np.float32), poses=poses,
+                  disps=(0.05 + 1.45 * r.random((B, h, w))).astype(np.float32))
+        ii_all, jj_all = np.concatenate([st["ii_inac"], st["ii"]]), np.concatenate([st["jj_inac"], st["jj"]])
+        norm = baseline_norm(poses, ii_all, jj_all)
+        short = norm < np.float32(MASK_THRESHOLD)
+        if (np.abs(norm - np.float32(MASK_THRESHOLD)) > 1e-4 * MASK_THRESHOLD).all() and short[-n_act:].any() \
+                and not short[-n_act:].all():
+            return st
+    raise AssertionError("no state with the margin and both kinds of baseline in 20 draws")
+
+
+def multi_tile_state(n_inac=1100, band=129, seed=23):
+    """random_state(12 keyframes, 48 active edges, 8x8 maps) with its `band` inactive edges repeated to n_inac entries
+    (repeated entries are legal in the list), every entry with a payload row of its own: the list spans two 1024-lane
+    tiles of the edge pass, and with band = 129 position 1024 falls among the last entries of a repetition, where the
+    selected and the unselected edges alternate"""
+    st = random_state(12, 48, band, 8, 8, seed)
+    r = np.random.default_rng(seed)
+    at = np.arange(n_inac) % band
+    shape = (1, n_inac, 8, 8, 2)
+    return dict(st, ii_inac=st["ii_inac"][at], jj_inac=st["jj_inac"][at],
+                target_inac=(r.normal(size=shape) * 20).astype(np.float32),
+                weight_inac=np.where(r.random(shape) < 0.1, 0.0, r.random(shape)).astype(np.float32))
+
+
+def selected_positions(st, inac_range, t0=None):
+    """the positions of the inactive list that :243 selects"""
+    if t0 is None:
+        t0 = max(1, int(st["ii"].min()) + 1)
+    return np.flatnonzero((st["ii_inac"] >= t0 - inac_range) & (st["jj_inac"] >= t0 - inac_range))
+
+
 def load_fixture(path):
     """-> [(name, state dict, parameter dict, recorded outputs dict)]"""
     out = []
