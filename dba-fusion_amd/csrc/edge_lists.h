@@ -1,6 +1,7 @@
 // Device helpers of the one-workgroup kernels that edit edge lists: select_edges_kernel (factors.hip),
-// add_factors_plan_kernel (add_factors.hip), update_inputs_edge_kernel (update_inputs.hip) and
-// filter_repeated_edges_kernel (proximity.hip).  Integer index work, no atomics: every result is in the input's order.
+// add_factors_plan_kernel (add_factors.hip), update_inputs_edge_kernel (update_inputs.hip), vio_window_plan_kernel
+// (vio_window.hip) and filter_repeated_edges_kernel (proximity.hip).  Integer index work, no atomics: every result is in
+// the input's order.
 // segment_reduce_kernel (upsample.hip) keeps a ballot compaction of its own: it is a many-workgroup throughput kernel
 // with another barrier placement.
 #pragma once

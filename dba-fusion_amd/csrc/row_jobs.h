@@ -1,5 +1,6 @@
 // The row mover's job table and copy body, shared by the launches that move payload rows (factors.hip: dba_move_rows,
-// dba_shift_rows; add_factors.hip: dba_add_factors_payload).  A job copies `count` rows of row_elems * width bytes,
+// dba_shift_rows; add_factors.hip: dba_add_factors_payload; vio_window.hip: dba_vio_window_payload).  A job copies
+// `count` rows of row_elems * width bytes,
 // dst[dst_row0 + r] = src[pos ? pos[r] : r]; the grid is the concatenation of every job's (row, chunk) pairs, a chunk
 // being 1024 elements of the job's vector width (16 KB at 16 bytes), four loads in flight per lane before the first
 // store.  Pure streaming: no LDS, plain vector stores.  A position outside [0, src_rows) copies nothing.

@@ -157,6 +157,9 @@ SYMBOLS = {
     "dba_update_inputs_payload": (c_int, [_P, _P, c_int, _P, _P, c_int, _P, _P, c_int, c_int, c_int, c_float, c_int,
                                           c_float] + [_P] * 5 + [c_int] * 3 + [_P] * 4),
     "dba_update_inputs_poll": (c_int, [ctypes.POINTER(c_int)]),
+    "dba_vio_window_plan": (c_int, [_P, _P, c_int] + [ctypes.c_int64] * 3 + [_P, _P, c_int, ctypes.c_int64] + [_P] * 8),
+    "dba_vio_window_payload": (c_int, [ctypes.POINTER(RowJob), c_int, _P, ctypes.POINTER(c_int), _P]),
+    "dba_vio_window_poll": (c_int, [ctypes.POINTER(c_int)]),
 }
 
 _lib = None

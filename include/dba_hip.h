@@ -781,6 +781,38 @@ int dba_update_inputs_payload(const float *target_inac, const float *weight_inac
                               float *damping_out, dba_stream_t stream);
 int dba_update_inputs_poll(int *counts6);
 
+/* ---- the window split of the VIO update (csrc/vio_window.hip) -------------------------------------------------------
+ * The statements of DepthVideo.ba's IMU branch that feed its two BACore.init calls (dbaf/depth_video.py:360-367, :388-390,
+ * :470-475) in two launches and no host synchronisation of their own.  Integers and bytes only: every result is exact.
+ * dba_vio_window_plan: one launch, one workgroup, no atomics.  Two selections, each compacted in list order:
+ *     marginalised  over the old window's lists (cur_ii, cur_jj)[n_cur]: last_t0 <= ii < lo && ii < last_t1 - 2 &&
+ *                   jj < last_t1 - 2 (:360-364); n_cur == 0: the branch is not entered, the marg_* outputs may be NULL
+ *     active        over the call's lists (ii, jj)[n >= 1]: ii >= t0 && jj >= t0 (:470)
+ *     marg_ii, marg_jj [n_cur], act_ii, act_jj [n] int64 out: the selected edges (:366-367, :471-472); behind the count the
+ *                   input's own entries at those positions
+ *     marg_pos [n_cur], act_pos [n] int32 out: the selected positions, position lists as dba_move_rows takes them; -1
+ *                   behind the count
+ *     res      [DBA_VW_RES_WORDS] int32 out: n_marg, max(marg_jj) (:372; -2^30 when nothing is selected), n_active,
+ *              min(ii) over the whole list (:475); indices are clamped to +-2^30
+ *   n_cur or n > 8192 is DBA_ERR_UNSUPPORTED; n == 0 is DBA_ERR_ARG.
+ * dba_vio_window_payload: ONE launch that executes up to DBA_VW_MAX_JOBS gathers dst[dst_row0 + r] = src[pos[r]], r in
+ *   [0, count), rows moved as dba_move_rows moves them (the same body and vector widths): marg_target, marg_weight
+ *   (:388-389), cur_target, cur_weight (:473-474).  expect4_host = the four words of res the jobs' counts and the caller's
+ *   eta views were taken from; the kernel compares them with res as the plan of THIS call left it.  On a mismatch every
+ *   job's rows are zeroed -- BACore with zero weights has nothing to linearise -- and a pinned host word is raised; nothing
+ *   outside the jobs' rows is written.  A call without rows still launches the comparison.
+ * dba_vio_window_poll: 1 when a payload launch reported a mismatch since the last poll (words8 = the plan's four words,
+ *   then the expected four), else 0.  Reads pinned host memory: no device synchronisation. */
+#define DBA_VW_RES_WORDS 4
+#define DBA_VW_MAX_JOBS 4
+int dba_vio_window_plan(const int64_t *cur_ii, const int64_t *cur_jj, int n_cur, int64_t last_t0, int64_t lo,
+                        int64_t last_t1, const int64_t *ii, const int64_t *jj, int n, int64_t t0, int64_t *marg_ii,
+                        int64_t *marg_jj, int *marg_pos, int64_t *act_ii, int64_t *act_jj, int *act_pos, int *res,
+                        dba_stream_t stream);
+int dba_vio_window_payload(const dba_row_job *jobs_host, int n_jobs, const int *res, const int *expect4_host,
+                           dba_stream_t stream);
+int dba_vio_window_poll(int *words8);
+
 #define DBA_PEER_TIMEOUT 1
 size_t dba_peer_exchange_bytes(size_t max_doubles);
 int dba_peer_exchange_create(size_t bytes, void **region, unsigned char *handle64);
