@@ -17,12 +17,10 @@
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
-#include <string.h>
-
-#include <mutex>
 
 #include "common.h"
 #include "edge_lists.h"
+#include "size_guard.h"
 
 namespace dba {
 
@@ -215,12 +213,8 @@ template <int PIX>
 __global__ __launch_bounds__(UI_PAY_THREADS) void update_inputs_payload_kernel(PayloadArgs a) {
   const int HW = a.HW;
   const bool ok = a.res[1] == a.exp_n_sel && a.res[2] == a.exp_N && a.res[3] == a.exp_n_kx && a.res[8] == 0;
-  if (!ok && blockIdx.x == 0 && threadIdx.x == 0) {
-    a.status[1] = a.res[1], a.status[2] = a.res[2], a.status[3] = a.res[3];
-    a.status[4] = a.exp_n_sel, a.status[5] = a.exp_N, a.status[6] = a.exp_n_kx;
-    __threadfence_system();
-    a.status[0] = 1;
-  }
+  if (!ok && blockIdx.x == 0 && threadIdx.x == 0)
+    guard_report<3>(a.status, {a.res[1], a.res[2], a.res[3]}, {a.exp_n_sel, a.exp_N, a.exp_n_kx});
   const unsigned bid = blockIdx.x;
   const unsigned row = bid / (unsigned)a.chunks, chunk = bid - row * (unsigned)a.chunks;
   const int p0 = ((int)chunk * UI_PAY_THREADS + (int)threadIdx.x) * PIX;
@@ -287,16 +281,9 @@ __global__ __launch_bounds__(UI_PAY_THREADS) void update_inputs_payload_kernel(P
   }
 }
 
-// the pinned, host-coherent words a mismatch is reported through (sticky until polled): [0] raised, [1..3] the counts
-// of the edge pass, [4..6] the counts the outputs were sized for
-struct UiStatus {
-  std::mutex mu;
-  int *words = nullptr;
-};
-static UiStatus &ui_status() {
-  static UiStatus s;
-  return s;
-}
+// a mismatch is reported through its words (size_guard.h): [1..3] the counts of the edge pass, [4..6] the counts the
+// outputs were sized for
+static SizeGuard ui_guard;
 
 }  // namespace dba
 
@@ -335,21 +322,11 @@ int dba_update_inputs_payload(const float *target_inac, const float *weight_inac
   if (far_rule && !disps) return DBA_ERR_ARG;
   if ((exp_N > 0 && (!target_out || !weight_out)) || (exp_n_kx > 0 && !damping_out)) return DBA_ERR_ARG;
   if (n_inac > DBA_SEL_MAX_EDGES || n_act > DBA_SEL_MAX_EDGES || n_frames > DBA_UI_MAX_FRAMES) return DBA_ERR_UNSUPPORTED;
-  UiStatus &st = ui_status();
-  {
-    std::lock_guard<std::mutex> lock(st.mu);
-    if (!st.words) {
-      void *p = nullptr;
-      DBA_HIP_CHECK(hipHostMalloc(&p, sizeof(int) * DBA_UI_RES_WORDS,
-                                  hipHostMallocCoherent | hipHostMallocMapped | hipHostMallocPortable));
-      memset(p, 0, sizeof(int) * DBA_UI_RES_WORDS);
-      st.words = static_cast<int *>(p);
-    }
-  }
   PayloadArgs a{};
+  if (const int rc = ui_guard.words(&a.status)) return rc;
   a.target_inac = target_inac, a.weight_inac = weight_inac, a.target_act = target_act, a.weight_act = weight_act;
   a.disps = disps, a.damping = damping, a.sel = sel, a.res = res, a.ii_out = ii_out, a.kx = kx, a.flags = flags;
-  a.target_out = target_out, a.weight_out = weight_out, a.damping_out = damping_out, a.status = st.words;
+  a.target_out = target_out, a.weight_out = weight_out, a.damping_out = damping_out;
   a.n_inac = n_inac, a.n_act = n_act, a.B = n_frames, a.HW = ht * wd;
   a.exp_n_sel = exp_n_sel, a.exp_N = exp_N, a.exp_n_kx = exp_n_kx, a.far_rule = far_rule ? 1 : 0;
   a.far_threshold = far_threshold, a.ep = ep;
@@ -374,16 +351,6 @@ int dba_update_inputs_payload(const float *target_inac, const float *weight_inac
   return DBA_OK;
 }
 
-int dba_update_inputs_poll(int *counts6) {
-  UiStatus &st = ui_status();
-  std::lock_guard<std::mutex> lock(st.mu);
-  if (!st.words) return 0;
-  volatile int *w = st.words;
-  if (!w[0]) return 0;
-  if (counts6)
-    for (int k = 0; k < 6; k++) counts6[k] = w[1 + k];
-  w[0] = 0;
-  return 1;
-}
+int dba_update_inputs_poll(int *counts6) { return ui_guard.poll(counts6, 6); }
 
 }  // extern "C"

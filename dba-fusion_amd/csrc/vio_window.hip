@@ -17,13 +17,11 @@
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
-#include <string.h>
-
-#include <mutex>
 
 #include "common.h"
 #include "edge_lists.h"
 #include "row_jobs.h"
+#include "size_guard.h"
 
 namespace dba {
 
@@ -125,12 +123,7 @@ struct VwGuard {
 __global__ __launch_bounds__(MOVE_THREADS) void vio_window_payload_kernel(RowTable<DBA_VW_MAX_JOBS> t, VwGuard g) {
   const int r0 = g.res[0], r1 = g.res[1], r2 = g.res[2], r3 = g.res[3];
   const bool ok = r0 == g.exp[0] && r1 == g.exp[1] && r2 == g.exp[2] && r3 == g.exp[3];
-  if (!ok && blockIdx.x == 0 && threadIdx.x == 0) {
-    g.status[1] = r0, g.status[2] = r1, g.status[3] = r2, g.status[4] = r3;
-    g.status[5] = g.exp[0], g.status[6] = g.exp[1], g.status[7] = g.exp[2], g.status[8] = g.exp[3];
-    __threadfence_system();
-    g.status[0] = 1;
-  }
+  if (!ok && blockIdx.x == 0 && threadIdx.x == 0) guard_report<4>(g.status, {r0, r1, r2, r3}, g.exp);
   if (blockIdx.x >= g.wgs) return;  // (a call that moves no row still runs the comparison, in one workgroup)
   RowTable<DBA_VW_MAX_JOBS> u = t;
 #pragma unroll
@@ -138,17 +131,9 @@ __global__ __launch_bounds__(MOVE_THREADS) void vio_window_payload_kernel(RowTab
   run_row_jobs<DBA_VW_MAX_JOBS, true>(u);
 }
 
-// the pinned, host-coherent words a mismatch is reported through (sticky until polled): [0] raised, [1..4] the plan's
-// result block, [5..8] the words the outputs were sized for
-struct VwStatus {
-  std::mutex mu;
-  int *words = nullptr;
-};
-static VwStatus &vw_status() {
-  static VwStatus s;
-  return s;
-}
-constexpr int VW_STATUS_WORDS = 16;
+// a mismatch is reported through its words (size_guard.h): [1..4] the plan's result block, [5..8] the words the outputs
+// were sized for
+static SizeGuard vw_guard;
 
 }  // namespace dba
 
@@ -181,20 +166,9 @@ int dba_vio_window_payload(const dba_row_job *jobs, int n_jobs, const int *res, 
     if (!push_job(t, wgs, (const char *)j.src, (char *)j.dst, j.pos, j.row_bytes, j.count, j.dst_row0, j.src_rows))
       return DBA_ERR_UNSUPPORTED;
   }
-  VwStatus &st = vw_status();
-  {
-    std::lock_guard<std::mutex> lock(st.mu);
-    if (!st.words) {
-      void *p = nullptr;
-      DBA_HIP_CHECK(hipHostMalloc(&p, sizeof(int) * VW_STATUS_WORDS,
-                                  hipHostMallocCoherent | hipHostMallocMapped | hipHostMallocPortable));
-      memset(p, 0, sizeof(int) * VW_STATUS_WORDS);
-      st.words = static_cast<int *>(p);
-    }
-  }
   VwGuard g{};
+  if (const int rc = vw_guard.words(&g.status)) return rc;
   g.res = res;
-  g.status = st.words;
   for (int k = 0; k < 4; k++) g.exp[k] = expect4[k];
   g.wgs = (unsigned)wgs;
   hipLaunchKernelGGL(vio_window_payload_kernel, dim3(wgs ? (unsigned)wgs : 1u), dim3(MOVE_THREADS), 0,
@@ -203,16 +177,6 @@ int dba_vio_window_payload(const dba_row_job *jobs, int n_jobs, const int *res, 
   return DBA_OK;
 }
 
-int dba_vio_window_poll(int *words8) {
-  VwStatus &st = vw_status();
-  std::lock_guard<std::mutex> lock(st.mu);
-  if (!st.words) return 0;
-  volatile int *w = st.words;
-  if (!w[0]) return 0;
-  if (words8)
-    for (int k = 0; k < 8; k++) words8[k] = w[1 + k];
-  w[0] = 0;
-  return 1;
-}
+int dba_vio_window_poll(int *words8) { return vw_guard.poll(words8, 8); }
 
 }  // extern "C"

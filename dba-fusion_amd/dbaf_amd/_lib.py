@@ -5,6 +5,7 @@ shared object is missing or a call fails, the product path raises -- it never co
 """
 import ctypes
 import os
+import weakref
 
 import torch
 
@@ -196,7 +197,7 @@ def check(rc, what):
         raise RuntimeError("dba_hip: %s failed with %s %s" % (what, msg, detail))
 
 
-# ---- what every ctypes caller of the edge-management entry points needs (factors, proximity, update_inputs) ----------
+# ---- what every ctypes caller of the edge-management entry points needs (factors, proximity, update_inputs, vio_window) ----
 
 def ptr(x):
     """the tensor's address as a void*; a null pointer for None and for an empty tensor"""
@@ -218,3 +219,48 @@ def check_edge_list(op, dev, x, nm):
             "%s must be a HIP device tensor%s; no CPU path" % (nm, "" if dev is None else " on %s" % dev))
     require(x.dtype == torch.int64 and x.dim() == 1 and x.is_contiguous(), op,
             "%s must be a contiguous 1-D int64 tensor" % nm)
+
+
+def dev_tensor(op, x, nm, dev, dtype, aligned=False):
+    """x must be a contiguous device tensor of `dtype`, on `dev` unless that is None; aligned: at a 16-byte boundary"""
+    require(isinstance(x, torch.Tensor) and x.is_cuda and (dev is None or x.device == dev), op,
+            "%s must be a HIP device tensor%s; no CPU path" % (nm, "" if dev is None else " on %s" % dev))
+    require(x.dtype == dtype, op, "%s must be %s, got %s" % (nm, dtype, x.dtype))
+    require(x.is_contiguous(), op, "%s must be contiguous" % nm)
+    require(not aligned or x.data_ptr() % 16 == 0, op, "%s must be 16-byte aligned" % nm)
+
+
+def edge_list(op, x, nm, dev, max_edges, aligned=False):
+    """dev_tensor for a 1-D int64 list of at most max_edges entries (update_inputs, vio_window; factors and proximity
+    keep check_edge_list, whose message texts are other ones)"""
+    dev_tensor(op, x, nm, dev, torch.int64, aligned)
+    require(x.dim() == 1, op, "%s must be 1-D, got %s" % (nm, tuple(x.shape)))
+    require(x.shape[0] <= max_edges, op, "%s: %d edges exceed the supported %d" % (nm, x.shape[0], max_edges))
+
+
+class EdgeSetMemo:
+    """What the first call on an edge set read from the device, for the later calls that read nothing.
+    An edge set is the identity of its list tensors (held weakly), their in-place versions and a key of host scalars.
+    The newest `capacity` sets are kept.  One instance per module: a report of the size guard clears its module's alone."""
+
+    def __init__(self, capacity=8):
+        self.capacity = capacity
+        self._entries = []   # (((weakref, _version), ...), key, value), newest last
+
+    def __len__(self):
+        return len(self._entries)
+
+    def lookup(self, lists, key):
+        """the value remembered for these tensor objects at these versions under `key` (the newest such), or None"""
+        for refs, k, value in reversed(self._entries):
+            if k == key and len(refs) == len(lists) and all(r() is x and v == x._version for (r, v), x in zip(refs, lists)):
+                return value
+        return None
+
+    def remember(self, lists, key, value):
+        live = [e for e in self._entries if all(r() is not None for r, _ in e[0])]
+        self._entries = live[max(0, len(live) - (self.capacity - 1)):]   # dead sets go, then all but the newest
+        self._entries.append((tuple((weakref.ref(x), x._version) for x in lists), key, value))
+
+    def clear(self):
+        del self._entries[:]

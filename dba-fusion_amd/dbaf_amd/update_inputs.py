@@ -34,12 +34,11 @@ unique), which stays the caller's statement before this call.
 `stats` counts the launches and host reads of this module since import (as dbaf_amd.factors.stats does).
 """
 import ctypes
-import weakref
 
 import torch
 
 from . import _lib
-from ._lib import ptr as _ptr, require as _require, stream as _stream
+from ._lib import ptr as _ptr, require as _require, stream as _stream, dev_tensor as _dev_tensor
 
 MAX_EDGES = 8192     # per list, the limit of dbaf_amd.factors
 MAX_FRAMES = 1024    # rows of video.poses
@@ -47,21 +46,7 @@ RES_WORDS = 16
 
 stats = dict(edge_launches=0, payload_launches=0, host_reads=0)
 
-_CACHE = []          # the edge sets whose counts are known, newest last
-_CACHE_MAX = 8
-
-
-def _dev_tensor(op, x, nm, dev, dtype):
-    _require(isinstance(x, torch.Tensor) and x.is_cuda and (dev is None or x.device == dev), op,
-             "%s must be a HIP device tensor%s; no CPU path" % (nm, "" if dev is None else " on %s" % dev))
-    _require(x.dtype == dtype, op, "%s must be %s, got %s" % (nm, dtype, x.dtype))
-    _require(x.is_contiguous(), op, "%s must be contiguous" % nm)
-
-
-def _edge_list(op, x, nm, dev):
-    _dev_tensor(op, x, nm, dev, torch.int64)
-    _require(x.dim() == 1, op, "%s must be 1-D, got %s" % (nm, tuple(x.shape)))
-    _require(x.shape[0] <= MAX_EDGES, op, "%s: %d edges exceed the supported %d" % (nm, x.shape[0], MAX_EDGES))
+_MEMO = _lib.EdgeSetMemo()   # the edge sets whose counts are known: key (t0, inac_range, B), value the counts dict
 
 
 def _payload(op, x, nm, dev, n, hw):
@@ -78,7 +63,7 @@ def _check_lists(op, ii, jj, ii_inac, jj_inac, poses):
     _require(isinstance(ii, torch.Tensor) and ii.is_cuda, op, "ii must be a HIP device tensor; no CPU path")
     dev = ii.device
     for x, nm in ((ii, "ii"), (jj, "jj"), (ii_inac, "ii_inac"), (jj_inac, "jj_inac")):
-        _edge_list(op, x, nm, dev)
+        _lib.edge_list(op, x, nm, dev, MAX_EDGES)
     _require(ii.shape == jj.shape, op, "ii and jj must have one length")
     _require(ii_inac.shape == jj_inac.shape, op, "ii_inac and jj_inac must have one length")
     _require(ii.shape[0] > 0, op, "no active edges (the reference's self.ii.min() raises too)")
@@ -92,25 +77,10 @@ def _check_lists(op, ii, jj, ii_inac, jj_inac, poses):
 def _raise_pending(lib):
     c = (ctypes.c_int * 6)()
     if lib.dba_update_inputs_poll(c):
-        del _CACHE[:]
+        _MEMO.clear()
         raise RuntimeError("update_inputs (MI355X): an earlier call's edge lists gave (n_sel, N, n_kx) = (%d, %d, %d) on the "
                            "device, its outputs were sized for (%d, %d, %d): an edge list was written without torch "
                            "noticing, or an index left [0, B).  That call returned zero weights." % tuple(c))
-
-
-def _lookup(lists, t0, inac_range, B):
-    for k in range(len(_CACHE) - 1, -1, -1):
-        ent = _CACHE[k]
-        if ent["t0"] == t0 and ent["inac_range"] == inac_range and ent["B"] == B and \
-                all(r() is x and v == x._version for (r, v), x in zip(ent["lists"], lists)):
-            return ent
-    return None
-
-
-def _remember(lists, t0, inac_range, B, counts):
-    ent = dict(lists=[(weakref.ref(x), x._version) for x in lists], t0=t0, inac_range=inac_range, B=B, counts=counts)
-    _CACHE[:] = [e for e in _CACHE if all(r() is not None for r, _ in e["lists"])][-(_CACHE_MAX - 1):]
-    _CACHE.append(ent)
 
 
 class _Edges:
@@ -193,12 +163,10 @@ def assemble(ii, jj, ii_inac, jj_inac, target, weight, target_inac, weight_inac,
             _require(0 <= c["n_sel"] <= n_inac and 0 <= c["N"] <= n_inac + n_act and 0 <= c["n_kx"] <= min(B, n_inac + n_act),
                      op, "_expect lies outside the edge pass's buffers")
         else:
-            ent = _lookup(lists, t0, inac_range, B)
-            if ent is None:
+            c = _MEMO.lookup(lists, (t0, inac_range, B))
+            if c is None:
                 c = _read_counts(op, e, B)
-                _remember(lists, t0, inac_range, B, c)
-            else:
-                c = ent["counts"]
+                _MEMO.remember(lists, (t0, inac_range, B), c)
         N, n_kx = c["N"], c["n_kx"]
         target_out = torch.empty(N, 2, ht, wd, dtype=torch.float32, device=dev)
         weight_out = torch.empty(N, 2, ht, wd, dtype=torch.float32, device=dev)

@@ -40,12 +40,11 @@ marg_jobs counts the row jobs of the marginalised set handed to payload launches
 """
 import collections
 import ctypes
-import weakref
 
 import torch
 
 from . import _lib
-from ._lib import ptr as _ptr, require as _require, stream as _stream
+from ._lib import ptr as _ptr, require as _require, stream as _stream, dev_tensor as _dev_tensor
 
 MAX_EDGES = 8192     # per list, the limit of dbaf_amd.factors
 RES_WORDS = 4        # n_marg, max(marg_jj), n_active, min(ii)
@@ -58,26 +57,11 @@ Cur = collections.namedtuple("Cur", "ii jj target weight eta")
 
 stats = dict(plan_launches=0, payload_launches=0, host_reads=0, marg_jobs=0)
 
-_CACHE = []          # the edge sets whose result blocks are known, newest last
-_CACHE_MAX = 8
-
-
-def _dev_tensor(op, x, nm, dev, dtype, aligned=True):
-    _require(isinstance(x, torch.Tensor) and x.is_cuda and (dev is None or x.device == dev), op,
-             "%s must be a HIP device tensor%s; no CPU path" % (nm, "" if dev is None else " on %s" % dev))
-    _require(x.dtype == dtype, op, "%s must be %s, got %s" % (nm, dtype, x.dtype))
-    _require(x.is_contiguous(), op, "%s must be contiguous" % nm)
-    _require(not aligned or x.data_ptr() % 16 == 0, op, "%s must be 16-byte aligned" % nm)
-
-
-def _edge_list(op, x, nm, dev):
-    _dev_tensor(op, x, nm, dev, torch.int64)
-    _require(x.dim() == 1, op, "%s must be 1-D, got %s" % (nm, tuple(x.shape)))
-    _require(x.shape[0] <= MAX_EDGES, op, "%s: %d edges exceed the supported %d" % (nm, x.shape[0], MAX_EDGES))
+_MEMO = _lib.EdgeSetMemo()   # the edge sets whose result blocks are known: value the block
 
 
 def _payload(op, x, nm, dev, n, hw):
-    _dev_tensor(op, x, nm, dev, torch.float32)
+    _dev_tensor(op, x, nm, dev, torch.float32, aligned=True)
     _require(x.dim() == 4 and x.shape[1] == 2, op, "%s must be [n, 2, ht, wd], got %s" % (nm, tuple(x.shape)))
     _require(x.shape[0] == n, op, "%s has %d edges, its edge list %d" % (nm, x.shape[0], n))
     _require(hw is None or tuple(x.shape[2:]) == hw, op, "%s maps are %s, expected %s" % (nm, tuple(x.shape[2:]), hw))
@@ -86,7 +70,7 @@ def _payload(op, x, nm, dev, n, hw):
 
 def _eta(op, x, nm, dev, hw):
     # no kernel reads it: it is sliced on the host alone, and the slice of an earlier call (s.cur.eta) starts anywhere
-    _dev_tensor(op, x, nm, dev, torch.float32, aligned=False)
+    _dev_tensor(op, x, nm, dev, torch.float32)
     _require(x.dim() == 3 and tuple(x.shape[1:]) == hw, op,
              "%s must be [rows, %d, %d], got %s" % (nm, hw[0], hw[1], tuple(x.shape)))
 
@@ -106,25 +90,10 @@ def _host_int(op, x, nm):
 def _raise_pending(lib):
     c = (ctypes.c_int * 8)()
     if lib.dba_vio_window_poll(c):
-        del _CACHE[:]
+        _MEMO.clear()
         raise RuntimeError("vio_window (MI355X): an earlier call's edge lists gave (n_marg, max marg_jj, n_active, min ii) = "
                            "(%d, %d, %d, %d) on the device, its outputs were sized for (%d, %d, %d, %d): an edge list was "
                            "written without torch noticing.  That call returned zero targets and weights." % tuple(c))
-
-
-def _lookup(lists, key):
-    for k in range(len(_CACHE) - 1, -1, -1):
-        ent = _CACHE[k]
-        if ent["key"] == key and len(ent["lists"]) == len(lists) and \
-                all(r() is x and v == x._version for (r, v), x in zip(ent["lists"], lists)):
-            return ent
-    return None
-
-
-def _remember(lists, key, block):
-    ent = dict(lists=[(weakref.ref(x), x._version) for x in lists], key=key, block=block)
-    _CACHE[:] = [e for e in _CACHE if all(r() is not None for r, _ in e["lists"])][-(_CACHE_MAX - 1):]
-    _CACHE.append(ent)
 
 
 def window_start(lo, t1, last_t0, last_t1):
@@ -159,8 +128,8 @@ def split_tensors(target, weight, eta, ii, jj, lo, t1, cur_ii, cur_jj, cur_targe
     op = "split"
     _require(isinstance(ii, torch.Tensor) and ii.is_cuda, op, "ii must be a HIP device tensor; no CPU path")
     dev = ii.device
-    _edge_list(op, ii, "ii", dev)
-    _edge_list(op, jj, "jj", dev)
+    _lib.edge_list(op, ii, "ii", dev, MAX_EDGES, aligned=True)
+    _lib.edge_list(op, jj, "jj", dev, MAX_EDGES, aligned=True)
     _require(ii.shape == jj.shape, op, "ii and jj must have one length")
     n = int(ii.shape[0])
     _require(n > 0, op, "no edges (the reference's ii.min() raises too)")
@@ -176,8 +145,8 @@ def split_tensors(target, weight, eta, ii, jj, lo, t1, cur_ii, cur_jj, cur_targe
         _require(cur_ii is not None and cur_jj is not None and cur_target is not None and cur_weight is not None
                  and cur_eta is not None, op,
                  "the marginalisation branch is entered (last_t0 = %d < lo = %d) but video.cur_* is None" % (last_t0, lo))
-        _edge_list(op, cur_ii, "cur_ii", dev)
-        _edge_list(op, cur_jj, "cur_jj", dev)
+        _lib.edge_list(op, cur_ii, "cur_ii", dev, MAX_EDGES, aligned=True)
+        _lib.edge_list(op, cur_jj, "cur_jj", dev, MAX_EDGES, aligned=True)
         _require(cur_ii.shape == cur_jj.shape, op, "cur_ii and cur_jj must have one length")
         n_cur = int(cur_ii.shape[0])
         _payload(op, cur_target, "cur_target", dev, n_cur, hw)
@@ -206,13 +175,11 @@ def split_tensors(target, weight, eta, ii, jj, lo, t1, cur_ii, cur_jj, cur_targe
                                            _ptr(act_lists), _ptr(act_lists[1]), _ptr(act_pos), _ptr(res), _stream(dev)),
                    "dba_vio_window_plan")
         stats["plan_launches"] += 1
-        ent = _lookup(lists, key)
-        if ent is None:
+        block = _MEMO.lookup(lists, key)
+        if block is None:
             block = tuple(res.cpu().tolist())   # the one host synchronisation of a first call
             stats["host_reads"] += 1
-            _remember(lists, key, block)
-        else:
-            block = ent["block"]
+            _MEMO.remember(lists, key, block)
         n_marg, max_mj, n_active, ii_min = block
         jobs = []
         marg = None

@@ -8,7 +8,8 @@
   - two calls chained through video.cur_* as the integration chains them, with odd edge counts and an eta view that
     starts off a 16-byte boundary, on 5x7 maps;
   - the argument errors; launches and host reads from `stats`; a later call under torch's sync debug mode; recording into
-    a hipGraph; the count guard; the hand-over to BACore.init + hessian in the deterministic accumulation mode."""
+    a hipGraph; the count guard, and that its report and update_inputs' stay apart; the hand-over to BACore.init + hessian
+    in the deterministic accumulation mode."""
 import ctypes
 import os
 import types
@@ -351,6 +352,60 @@ def test_guard_writes_zero_rows_and_the_next_call_raises():
     job[0].count = cnt + 1
     assert lib.dba_vio_window_payload(job, 1, p(res), (ctypes.c_int * 4)(*block), stream) == -1
     assert lib.dba_vio_window_payload(job, 5, p(res), (ctypes.c_int * 4)(*block), stream) == -1
+
+
+def test_reports_of_the_two_size_guards_stay_apart():
+    """vio_window.split and update_inputs.assemble take their guard from one header (csrc/size_guard.h), each with pinned
+    words of its own: a mismatch of one is polled by that one alone.  70 edges (a full wave and a partial one), 4x6
+    maps; the mismatches are the designed path, through the C ABI as in the guard tests of the two modules."""
+    import update_inputs_model as um
+    from dbaf_amd import update_inputs as ux
+    lib, stream = _lib.load(), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    p = lambda x: ctypes.c_void_p(x.data_ptr())  # noqa: E731
+    words, counts = (ctypes.c_int * 8)(), (ctypes.c_int * 6)()
+    assert lib.dba_vio_window_poll(words) == 0 and lib.dba_update_inputs_poll(counts) == 0
+    n, h, w, cnt = 70, 4, 6, 3
+    # a valid 70-edge state of update_inputs, and its edge pass
+    ust = um.random_state(12, n, n, h, w, 29)
+    g = types.SimpleNamespace(**{k: _t(v) for k, v in ust.items()})
+    B = int(g.poses.shape[0])
+    c = ux.edge_counts(g.ii, g.jj, g.ii_inac, g.jj_inac, g.poses, 3)
+    assert c["N"] - c["n_sel"] == n and c["n_sel"] > 3 and c["n_kx"] > 1
+    # the window split's payload launch with a wrong fourth word: a 3-row job
+    st, sc = vm.random_state(n, 0, h, w, 31, "ahead_mixed")
+    video, d = to_device(st, sc)
+    want = vm.split(st, **sc)
+    lists, pos, res = torch.empty(2, n, dtype=torch.int64, device=DEV), torch.empty(n, dtype=torch.int32, device=DEV), \
+        torch.empty(4, dtype=torch.int32, device=DEV)
+    assert lib.dba_vio_window_plan(None, None, 0, sc["last_t0"], sc["lo"], sc["last_t1"], p(d["ii"]), p(d["jj"]), n, want["t0"],
+                                   None, None, None, p(lists), p(lists[1]), p(pos), p(res), stream) == 0
+    block = res.cpu().tolist()
+    assert block == [0, -(1 << 30), len(want["cur"]["ii"]), want["ii_min"]] and block[2] >= cnt
+    dst = torch.full((cnt, 2, h, w), 7.0, device=DEV)
+    job = (_lib.RowJob * 4)(_lib.RowJob(d["weight"].data_ptr(), dst.data_ptr(), pos.data_ptr(), 2 * h * w * 4, cnt, 0, n, cnt))
+    wrong = block[:3] + [block[3] + 1]
+    assert lib.dba_vio_window_payload(job, 1, p(res), (ctypes.c_int * 4)(*wrong), stream) == 0
+    torch.cuda.synchronize()
+    assert not bool(dst.any())
+    assert lib.dba_update_inputs_poll(counts) == 0
+    assert ux.edge_counts(g.ii, g.jj, g.ii_inac, g.jj_inac, g.poses, 3) == c        # polls update_inputs' words: nothing
+    assert lib.dba_vio_window_poll(words) == 1 and list(words) == block + wrong
+    assert lib.dba_vio_window_poll(words) == 0
+    # mirrored: update_inputs' payload launch with a wrong exp_N (and exp_n_kx), as its count-guard test launches it
+    e = ux._edge_pass(lib, torch.device(DEV), B, g.ii, g.jj, g.ii_inac, g.jj_inac, g.poses, None, 3, um.MASK_THRESHOLD, True)
+    exp_N, exp_kx = c["N"] - 3, c["n_kx"] - 1
+    bufs = [torch.full((exp_N, 2, h, w), 7.0, device=DEV), torch.full((exp_N, 2, h, w), 7.0, device=DEV),
+            torch.full((exp_kx, h, w), 7.0, device=DEV)]
+    assert lib.dba_update_inputs_payload(p(g.target_inac), p(g.weight_inac), n, p(g.target), p(g.weight), n, p(g.disps),
+                                         p(g.damping), B, h, w, um.FAR_THRESHOLD, 1, 1e-7, p(e.sel), p(e.ii), p(e.flags),
+                                         p(e.kx), p(e.res), c["n_sel"], exp_N, exp_kx, p(bufs[0]), p(bufs[1]), p(bufs[2]),
+                                         stream) == 0
+    torch.cuda.synchronize()
+    assert not bool(bufs[0].any()) and not bool(bufs[1].any()) and bool((bufs[2] == np.float32(1e-7)).all())
+    assert lib.dba_vio_window_poll(words) == 0
+    assert lib.dba_update_inputs_poll(counts) == 1
+    assert tuple(counts) == (c["n_sel"], c["N"], c["n_kx"], c["n_sel"], exp_N, exp_kx)
+    assert lib.dba_update_inputs_poll(counts) == 0
 
 
 # ---- the hand-over -------------------------------------------------------------------------------------------------------
