@@ -59,7 +59,26 @@ struct ShReproj {
   const int64_t *ii, *jj;
   float2 *coords_out;  // [n, h1, w1, 2] or null
   float *valid_out;    // [n, h1, w1, 1] or null
+  // the motion features of the same pixels (covisible_graph.py:221-222), read and written by the MOTN instantiations of the
+  // lookup kernels only (dba_corr_lookup_reproject_motion_sheared); null on every other path
+  const float2 *target_in;  // [n, h1, w1, 2]: the edge's previous target
+  float *motn_out;          // [n, 4, h1, w1] planar
 };
+
+// torch.clamp(v, -64, 64) as torch's device kernel computes it: a compare-select that hands a NaN through (fminf / fmaxf
+// would drop it)
+__device__ __forceinline__ float sh_clamp64(float v) { return v < -64.0f ? -64.0f : (v > 64.0f ? 64.0f : v); }
+
+// motn = cat([coords1 - coords0, target - coords1], -1).permute(0,1,4,2,3).clamp(-64, 64) for one pixel: coords0 is the
+// pixel's own (x1, y1) (pops.coords_grid), each value one float32 subtraction and the clamp
+__device__ __forceinline__ void sh_motion(const ShReproj &RP, size_t e, int HW1, int plin, float2 c, float x1, float y1) {
+  const float2 t = RP.target_in[e * HW1 + plin];
+  float *m = RP.motn_out + e * 4 * HW1 + plin;
+  m[0] = sh_clamp64(__fsub_rn(c.x, x1));
+  m[HW1] = sh_clamp64(__fsub_rn(c.y, y1));
+  m[2 * (size_t)HW1] = sh_clamp64(__fsub_rn(t.x, c.x));
+  m[3 * (size_t)HW1] = sh_clamp64(__fsub_rn(t.y, c.y));
+}
 
 // ---- reference layout -> sheared layout, one pyramid level ------------------------------------------
 // block = (x1 tile of 64, ty, n*h1 + y1): loads V[n][y1][x1 tile][ty][0..w2l) and writes, for every dx,
@@ -256,7 +275,9 @@ __device__ __forceinline__ int sh2_mod(int v, int n, float inv_n, bool pow2) {
   return m;
 }
 
-template <int R>
+// MOTN: the level-0 waves also write the motion features (ShReproj::target_in / motn_out); a template parameter, so that the
+// instantiations without it compile to what they were before it existed (profiles/update_step_lookup_resources.txt)
+template <int R, bool MOTN>
 __global__ __launch_bounds__(SH2_WAVES * 64, SH2_MINOCC_CFG) void corr_lookup_resident_kernel(
     ShLevels L, const float2 *__restrict__ coords, _Float16 *__restrict__ out, int n, int h1, int w1, int h2, int w2,
     int num_levels, int HW1p, float inv_w1, int lvl0, int cflags, const int *__restrict__ slots, ShReproj RP, int tiled, int w1g) {
@@ -314,6 +335,7 @@ __global__ __launch_bounds__(SH2_WAVES * 64, SH2_MINOCC_CFG) void corr_lookup_re
     if (lvl == 0 && active) {
       if (RP.coords_out) RP.coords_out[(size_t)e * HW1 + plin] = cxy;
       if (RP.valid_out) RP.valid_out[(size_t)e * HW1 + plin] = ok;
+      if constexpr (MOTN) sh_motion(RP, (size_t)e, HW1, plin, cxy, (float)x1, (float)y1);
     }
   } else {
     cxy = sh_coord(coords, cplanar, (size_t)e, HW1, plin);
@@ -559,7 +581,7 @@ constexpr int SB_TILES = 4;
 #define SB_DEPTH 2
 #endif
 
-template <int R>
+template <int R, bool MOTN>
 __global__ __launch_bounds__(256, SB_MIN_WAVES) void corr_lookup_rowtile_kernel(ShLevels L, const float2 *__restrict__ coords,
                                                                   _Float16 *__restrict__ out, int n, int h1, int w1, int h2,
                                                                   int w2, int num_levels, int lvl0, int cflags,
@@ -611,6 +633,7 @@ __global__ __launch_bounds__(256, SB_MIN_WAVES) void corr_lookup_rowtile_kernel(
     if (lvl == 0 && pvalid) {
       if (RP.coords_out) RP.coords_out[(size_t)e * HW1 + pix] = cxy;
       if (RP.valid_out) RP.valid_out[(size_t)e * HW1 + pix] = ok;
+      if constexpr (MOTN) sh_motion(RP, (size_t)e, HW1, (int)pix, cxy, (float)x1, (float)y1);
     }
   } else {
     cxy = sh_coord(coords, cplanar, (size_t)e, HW1, (int)pix);
@@ -943,9 +966,10 @@ int dba_corr_shear_level_slots(const void *ref_level, void *sheared_store, const
 }
 
 // levels [lvl0, lvl0 + nlv) of the pyramid -> corr [n, nlv, 49, h1, w1]
-static int lookup_sheared_launch(const ShLevels &L, const float *coords, void *corr, int n, int h1, int w1, int h2, int w2,
-                                 int lvl0, int nlv, int cflags, dba_stream_t stream, const int *slots = nullptr,
-                                 const ShReproj &RP = ShReproj{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}) {
+extern "C++" {   // (a template inside the C block)
+template <bool MOTN>
+static int lookup_sheared_launch_t(const ShLevels &L, const float *coords, void *corr, int n, int h1, int w1, int h2, int w2,
+                                   int lvl0, int nlv, int cflags, dba_stream_t stream, const int *slots, const ShReproj &RP) {
   if ((long)n * h1 * w1 >= 2147483647L) return DBA_ERR_UNSUPPORTED;
   const int HW1p = dba_corr_sheared_plane_elems(h1, w1);
   // "rows over tiles" on tiled planes (maps whose rows are whole 64-pixel segments, common.h), "resident" on every other
@@ -958,7 +982,7 @@ static int lookup_sheared_launch(const ShLevels &L, const float *coords, void *c
   const bool rowtile_ok = tiled && SH_TW == 16 && (w1g & 63) == 0 && (size_t)(h2 >> lvl0) * (w2 >> lvl0) * HW1p * 2 < ((size_t)1 << 31);
   if ((sel == 5 || sel == 0) && rowtile_ok) {   // loaders per tile, workers per map row
     dim3 grid((unsigned)((long)n * (h1g / 4) * (w1g / 64)), nlv);
-    hipExtLaunchKernelGGL((corr_lookup_rowtile_kernel<3>), grid, dim3(256), 0, (hipStream_t)stream, e0, e1, 0, L,
+    hipExtLaunchKernelGGL((corr_lookup_rowtile_kernel<3, MOTN>), grid, dim3(256), 0, (hipStream_t)stream, e0, e1, 0, L,
                           reinterpret_cast<const float2 *>(coords), static_cast<_Float16 *>(corr), n, h1, w1, h2, w2, nlv, lvl0,
                           cflags, slots, RP, h1g, w1g);
     DBA_LAUNCH_CHECK();
@@ -970,16 +994,25 @@ static int lookup_sheared_launch(const ShLevels &L, const float *coords, void *c
   if (lds > 64 * 1024) {
     static DeviceOnce attr_once;
     if (attr_once.needed()) {
-      DBA_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&corr_lookup_resident_kernel<3>),
+      DBA_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&corr_lookup_resident_kernel<3, MOTN>),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
       attr_once.done();
     }
   }
-  hipExtLaunchKernelGGL((corr_lookup_resident_kernel<3>), grid, dim3(SH2_WAVES * 64), lds, (hipStream_t)stream, e0, e1, 0, L,
+  hipExtLaunchKernelGGL((corr_lookup_resident_kernel<3, MOTN>), grid, dim3(SH2_WAVES * 64), lds, (hipStream_t)stream, e0, e1, 0, L,
                         reinterpret_cast<const float2 *>(coords), static_cast<_Float16 *>(corr), n, h1, w1, h2, w2,
                         nlv, HW1p, 1.0f / (float)w1, lvl0, cflags, slots, RP, tiled, w1g);
   DBA_LAUNCH_CHECK();
   return DBA_OK;
+}
+
+}  // extern "C++"
+
+static int lookup_sheared_launch(const ShLevels &L, const float *coords, void *corr, int n, int h1, int w1, int h2, int w2,
+                                 int lvl0, int nlv, int cflags, dba_stream_t stream, const int *slots = nullptr,
+                                 const ShReproj &RP = ShReproj{}) {
+  if (RP.motn_out) return lookup_sheared_launch_t<true>(L, coords, corr, n, h1, w1, h2, w2, lvl0, nlv, cflags, stream, slots, RP);
+  return lookup_sheared_launch_t<false>(L, coords, corr, n, h1, w1, h2, w2, lvl0, nlv, cflags, stream, slots, RP);
 }
 
 int dba_corr_lookup_pyramid_sheared(const void *const *volumes, const float *coords_nhw2, void *corr, int n, int h1,
@@ -1050,7 +1083,26 @@ int dba_corr_lookup_reproject_sheared(const void *const *volumes, const int *slo
   if ((h2 >> (num_levels - 1)) < 1 || (w2 >> (num_levels - 1)) < 1) return DBA_ERR_ARG;
   ShLevels L;
   for (int l = 0; l < SH_MAX_LEVELS; l++) L.vol[l] = (l < num_levels) ? static_cast<const _Float16 *>(volumes[l]) : nullptr;
-  const ShReproj RP{poses, disps, intrinsics_b4, ii, jj, reinterpret_cast<float2 *>(coords_out), valid_out};
+  const ShReproj RP{poses, disps, intrinsics_b4, ii, jj, reinterpret_cast<float2 *>(coords_out), valid_out, nullptr, nullptr};
+  return lookup_sheared_launch(L, nullptr, corr, n, h1, w1, h2, w2, 0, num_levels, 4, stream, slots, RP);
+}
+
+int dba_corr_lookup_reproject_motion_sheared(const void *const *volumes, const int *slots, const float *poses,
+                                             const float *disps, const float *intrinsics_b4, const int64_t *ii,
+                                             const int64_t *jj, float *coords_out, float *valid_out, void *corr,
+                                             const float *target, float *motn, int n, int h1, int w1, int h2, int w2,
+                                             int num_levels, int radius, dba_stream_t stream) {
+  if (n < 0 || h1 <= 0 || w1 <= 0 || h2 <= 0 || w2 <= 0 || num_levels < 1 || num_levels > SH_MAX_LEVELS)
+    return DBA_ERR_ARG;
+  if (radius != 3) return DBA_ERR_UNSUPPORTED;
+  if (n == 0) return DBA_OK;
+  if (!volumes || !poses || !disps || !intrinsics_b4 || !ii || !jj || !corr || !target || !motn) return DBA_ERR_ARG;
+  if ((uintptr_t)target % 8 || (uintptr_t)motn % 4) return DBA_ERR_ARG;   // target is read as (x, y) pairs
+  if ((h2 >> (num_levels - 1)) < 1 || (w2 >> (num_levels - 1)) < 1) return DBA_ERR_ARG;
+  ShLevels L;
+  for (int l = 0; l < SH_MAX_LEVELS; l++) L.vol[l] = (l < num_levels) ? static_cast<const _Float16 *>(volumes[l]) : nullptr;
+  const ShReproj RP{poses, disps, intrinsics_b4, ii, jj, reinterpret_cast<float2 *>(coords_out), valid_out,
+                    reinterpret_cast<const float2 *>(target), motn};
   return lookup_sheared_launch(L, nullptr, corr, n, h1, w1, h2, w2, 0, num_levels, 4, stream, slots, RP);
 }
 

@@ -119,6 +119,7 @@ SYMBOLS = {
     "dba_corr_lookup_pyramid_sheared_slots": (c_int, [_P, _P, _P, _P] + [c_int] * 7 + [_P]),
     "dba_corr_lookup_pyramid_slots": (c_int, [_P, _P, _P, _P] + [c_int] * 8 + [_P]),
     "dba_corr_lookup_reproject_sheared": (c_int, [_P] * 10 + [c_int] * 7 + [_P]),
+    "dba_corr_lookup_reproject_motion_sheared": (c_int, [_P] * 12 + [c_int] * 7 + [_P]),
     "dba_corr_index_backward": (c_int, [_P, _P, _P] + [c_int] * 6 + [_P]),
     "dba_corr_volume_scratch_bytes": (c_size_t, [c_int] * 6),
     "dba_corr_once_pyramid_bytes": (c_size_t, [c_int] * 6),
@@ -157,6 +158,8 @@ SYMBOLS = {
                                         c_float, c_int] + [_P] * 7),
     "dba_update_inputs_payload": (c_int, [_P, _P, c_int, _P, _P, c_int, _P, _P, c_int, c_int, c_int, c_float, c_int,
                                           c_float] + [_P] * 5 + [c_int] * 3 + [_P] * 4),
+    "dba_update_inputs_payload_op": (c_int, [_P, _P, c_int, _P, _P, _P, c_int, c_int, _P, _P, c_int, c_int, c_int, c_float,
+                                             c_int, c_float] + [_P] * 5 + [c_int] * 3 + [_P] * 6),
     "dba_update_inputs_poll": (c_int, [ctypes.POINTER(c_int)]),
     "dba_vio_window_plan": (c_int, [_P, _P, c_int] + [ctypes.c_int64] * 3 + [_P, _P, c_int, ctypes.c_int64] + [_P] * 8),
     "dba_vio_window_payload": (c_int, [ctypes.POINTER(RowJob), c_int, _P, ctypes.POINTER(c_int), _P]),

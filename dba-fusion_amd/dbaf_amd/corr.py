@@ -394,6 +394,25 @@ class CorrBlock:
         poses [B,7] (or [1,B,7] / an SE3), disps [B,h,w] (or [1,B,h,w]), intrinsics [B,4] / [1,B,4] / [4]; ii, jj [n].
         Returns (corr [1,n,L*49,h,w], coords [1,n,h,w,2], valid [1,n,h,w,1]) -- corr and coords bit-identical to
         projective_transform followed by __call__."""
+        return self._lookup_reprojected(poses, disps, intrinsics, ii, jj, None, timing)
+
+    def lookup_motion(self, poses, disps, intrinsics, ii, jj, target, timing=None):
+        """lookup_reprojected with the motion features of CovisibleGraph.update() (covisible_graph.py:221-222) written by
+        the same launch: target [1,n,h,w,2] or [n,h,w,2] float32 contiguous is the edges' previous target (self.target).
+        Returns (corr, coords, valid, motn), motn [1,n,4,h,w] float32 =
+            torch.cat([coords - coords0, target - coords], dim=-1).permute(0,1,4,2,3).clamp(-64.0, 64.0)
+        bit for bit (a NaN passes the clamp, as it does torch's); corr, coords and valid are lookup_reprojected's bytes."""
+        op = "lookup_motion"
+        _lib.require(isinstance(target, torch.Tensor) and target.is_cuda, op, "target must be a HIP device tensor; no CPU path")
+        _lib.require(target.dtype == torch.float32, op, "target must be float32, got %s" % target.dtype)
+        shape = tuple(target.shape[1:]) if (target.dim() == 5 and target.shape[0] == 1) else tuple(target.shape)
+        _lib.require(shape == (self.n, self.h1, self.w1, 2), op, "target must be [1, %d, %d, %d, 2] or without the leading 1, "
+                     "got %s" % (self.n, self.h1, self.w1, tuple(target.shape)))
+        _lib.require(target.is_contiguous(), op, "target must be contiguous")
+        _lib.require(target.data_ptr() % 8 == 0, op, "target must be 8-byte aligned (it is read as (x, y) pairs)")
+        return self._lookup_reprojected(poses, disps, intrinsics, ii, jj, target, timing)
+
+    def _lookup_reprojected(self, poses, disps, intrinsics, ii, jj, target, timing):
         if self.layout != "sheared":
             raise RuntimeError("lookup_reprojected needs the flow-aligned layout")
         self._materialise()
@@ -415,6 +434,15 @@ class CorrBlock:
         if timing is not None:
             lib.dba_corr_lookup_arm_timing(ctypes.c_void_p(timing[0].cuda_event), ctypes.c_void_p(timing[1].cuda_event))
         slots = None if self._identity else self._slots
+        if target is not None:
+            _lib.require(target.device == d.device, "lookup_motion", "target must be on %s" % d.device)
+            motn = torch.empty(1, n, 4, ht, wd, dtype=torch.float32, device=d.device)
+            _lib.check(lib.dba_corr_lookup_reproject_motion_sheared(self._store_ptrs(), _ptr(slots), _ptr(pdata), _ptr(d),
+                                                                    _ptr(K), _ptr(ii), _ptr(jj), _ptr(coords), _ptr(valid),
+                                                                    _ptr(out), _ptr(target), _ptr(motn), n, ht, wd, self.h2,
+                                                                    self.w2, self.num_levels, self.radius, _stream()),
+                       "dba_corr_lookup_reproject_motion_sheared")
+            return out, coords, valid, motn
         _lib.check(lib.dba_corr_lookup_reproject_sheared(self._store_ptrs(), _ptr(slots), _ptr(pdata), _ptr(d), _ptr(K),
                                                          _ptr(ii), _ptr(jj), _ptr(coords), _ptr(valid), _ptr(out), n, ht, wd,
                                                          self.h2, self.w2, self.num_levels, self.radius, _stream()),

@@ -448,6 +448,20 @@ int dba_corr_lookup_reproject_sheared(const void *const *level_stores, const int
                                       float *coords_out, float *valid_out, void *corr, int n, int h1, int w1, int h2, int w2,
                                       int num_levels, int radius, dba_stream_t stream);
 
+/* The same launch with the motion features of CovisibleGraph.update() riding along (dbaf/covisible_graph.py:221-222):
+ *     motn = torch.cat([coords1 - coords0, target - coords1], dim=-1).permute(0,1,4,2,3).clamp(-64.0, 64.0)
+ * target [n,h1,w1,2] f32 is the edges' previous target (pixel-interleaved, 8-byte aligned), motn [n,4,h1,w1] f32 (planar)
+ * receives, from the lane of pyramid level 0 that writes the pixel's coords_out, clamp(cx - x1), clamp(cy - y1),
+ * clamp(tx - cx), clamp(ty - cy): one float32 subtraction each, coords0 = the pixel's own (x1, y1), and a clamp that is a
+ * compare-select, so a NaN passes as it does through torch.clamp.  Bit-identical to the two statements run with torch on
+ * the device; corr, coords_out and valid_out are the bytes dba_corr_lookup_reproject_sheared writes.  target and motn
+ * must not be NULL; the kernels are instantiations of their own, the lookups above are compiled as before. */
+int dba_corr_lookup_reproject_motion_sheared(const void *const *level_stores, const int *slots, const float *poses,
+                                             const float *disps, const float *intrinsics_b4, const int64_t *ii,
+                                             const int64_t *jj, float *coords_out, float *valid_out, void *corr,
+                                             const float *target, float *motn, int n, int h1, int w1, int h2, int w2,
+                                             int num_levels, int radius, dba_stream_t stream);
+
 /* A pyramid that is built, looked up ONCE and dropped -- MotionFilter.track, dbaf/motion_filter.py:74-76:
  * `corr = CorrBlock(self.fmap[None,[0]], gmap[None,[0]])(coords0)`, once per incoming frame -- as one call: the levels go into
  * `pyramid` (device scratch of dba_corr_once_pyramid_bytes bytes that the caller keeps per stream and reuses from frame to frame:
@@ -765,6 +779,19 @@ int dba_add_factors_payload(const dba_af_job *jobs_host, int n_jobs, const dba_a
  *   call with zero weights changes nothing -- and raises a pinned host word; it reads and writes nothing outside
  *   [0, exp_N) / [0, exp_n_kx) rows.  Pointers must be 8-byte aligned; 16-byte loads and stores where ht * wd is a multiple
  *   of 4 and the pointers allow.
+ * dba_update_inputs_payload_op: dba_update_inputs_payload with the ACTIVE rows taken from the update operator's outputs
+ *   instead of (target_act, weight_act) -- the two statements in front of the ones above (:235-236):
+ *       target = coords1 + delta.to(float)   one float32 rounding        weight = weight.to(float)
+ *   coords1 [n_act, ht, wd, 2] f32; delta, weight_op [n_act, ht, wd, 2] in op_dtype = DBA_F32 or DBA_F16 (a float16 widens
+ *   exactly; another dtype is DBA_ERR_UNSUPPORTED).  target_new, weight_new [n_act, ht, wd, 2] f32 out, pixel-interleaved:
+ *   what the caller assigns to self.target / self.weight, the weight BEFORE any rule (the rules act on the concatenated
+ *   copy).  The lane that made an active row's values carries them on into the planar rows and the weight rules.  The
+ *   launch reads neither target_new nor weight_new, so they may be the tensors the NEXT lookup reads.  Inactive and
+ *   damping rows, the guard and the planar outputs are those of dba_update_inputs_payload; target_new / weight_new depend
+ *   on no count and are written for all n_act rows whatever the guard says (rows that outputs sized for other counts do not
+ *   reach get workgroups of their own).  Alignment: every float32 pointer 8 bytes, delta / weight_op 8 bytes in float32
+ *   and 4 in float16 (a pixel's pair); 16-byte loads and stores where ht * wd is a multiple of 4 and EVERY pointer, the
+ *   float16 ones included (8 values = 4 pixels per lane), is 16-byte aligned, else the one-pixel path.
  * dba_update_inputs_poll: 1 when a payload pass reported a mismatch since the last poll (counts6 = the edge pass's n_sel,
  *   N, n_kx, then the expected three), else 0.  Reads pinned host memory: no device synchronisation. */
 #define DBA_UI_MAX_FRAMES 1024
@@ -779,6 +806,13 @@ int dba_update_inputs_payload(const float *target_inac, const float *weight_inac
                               const int64_t *ii_out, const unsigned char *flags, const int64_t *kx, const int *res,
                               int exp_n_sel, int exp_N, int exp_n_kx, float *target_out, float *weight_out,
                               float *damping_out, dba_stream_t stream);
+int dba_update_inputs_payload_op(const float *target_inac, const float *weight_inac, int n_inac, const float *coords1,
+                                 const void *delta, const void *weight_op, int op_dtype, int n_act, const float *disps,
+                                 const float *damping, int n_frames, int ht, int wd, float far_threshold, int far_rule,
+                                 float ep, const int *sel, const int64_t *ii_out, const unsigned char *flags,
+                                 const int64_t *kx, const int *res, int exp_n_sel, int exp_N, int exp_n_kx,
+                                 float *target_out, float *weight_out, float *damping_out, float *target_new,
+                                 float *weight_new, dba_stream_t stream);
 int dba_update_inputs_poll(int *counts6);
 
 /* ---- the window split of the VIO update (csrc/vio_window.hip) -------------------------------------------------------
