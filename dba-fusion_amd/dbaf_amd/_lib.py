@@ -164,6 +164,11 @@ SYMBOLS = {
     "dba_vio_window_plan": (c_int, [_P, _P, c_int] + [ctypes.c_int64] * 3 + [_P, _P, c_int, ctypes.c_int64] + [_P] * 8),
     "dba_vio_window_payload": (c_int, [ctypes.POINTER(RowJob), c_int, _P, ctypes.POINTER(c_int), _P]),
     "dba_vio_window_poll": (c_int, [ctypes.POINTER(c_int)]),
+    "dba_keyframe_report_words": (c_int, []),
+    "dba_keyframe_report": (c_int, [_P, ctypes.POINTER(_P), ctypes.POINTER(c_int)]),
+    "dba_keyframe_check": (c_int, [_P] * 3 + [c_int] * 4 + [c_float, _P, c_int, _P]),
+    "dba_keyframe_flow_magnitude": (c_int, [_P, c_int, c_int, _P, c_int, _P]),
+    "dba_keyframe_wait": (c_int, [_P, c_int]),
 }
 
 _lib = None

@@ -847,6 +847,46 @@ int dba_vio_window_payload(const dba_row_job *jobs_host, int n_jobs, const int *
                            dba_stream_t stream);
 int dba_vio_window_poll(int *words8);
 
+/* ---- keyframe gating (csrc/keyframe.hip) ----------------------------------------------------------------------------
+ * The two per-frame decisions the host takes from device data, each in ONE launch of one workgroup and ONE host wait.  The
+ * launch writes a report into pinned, host-coherent 32-bit words owned by the library and then a completion word; the host
+ * spins on that word (BACore.hessian's hand-over).  Neither the launches nor the wait synchronises the stream.
+ * dba_keyframe_report_words: the words of a report, DBA_KF_WORDS.  Layout: [DBA_KF_D] d or the flow magnitude (float),
+ *   [DBA_KF_WIN] the window length, 7 or 3 (int), [DBA_KF_CAM .. +7) cam_translation (float; 0 behind the window),
+ *   [DBA_KF_MAT .. +16) the 4x4 matrix, row-major (float), [DBA_KF_SEQ] the completion word (int).
+ * dba_keyframe_report: *report = the block of (current device, stream), allocated zeroed at first use and never freed while
+ *   the process lives, *seq = its next sequence number (1, 2, ...).  A block serves one call at a time: a later launch
+ *   overwrites it, so the host copies what it needs before it asks for the block again.
+ * dba_keyframe_check: dbaf/dbaf_frontend.py:262-264 and :319-324 up to the host's comparisons.
+ *     d    = DepthVideo.distance([t1-3], [t1-2], beta, bidirectional=True): lanes 0-255 and 256-511 run
+ *            dba_frame_distance's per-pair arithmetic for (t1-3, t1-2) and (t1-2, t1-3); bit-identical to
+ *            dba_frame_distance_bidir on that pair, the 1000 sentinel of a pair with < 75 % valid weight included;
+ *     cam  = torch.norm((poses[k0:t1-3] * poses[t1-2].inv()[None]).translation()[:, 0:3], dim=1), k0 = t1-10 when
+ *            t1 > 10, else t1-6: cam[k] = |qrot(q_k, t_inv) + t_k|, (t_inv, q_inv) = inv(poses[t1-2]);
+ *     mat  = poses[t1-1].inv().matrix();
+ *   cam and mat in float32 with unfused operations in the order of the lietorch shim's formulas.  poses [n_frames,7],
+ *   disps [n_frames,ht,wd], intrinsics [4] f32.  Only pose rows [k0, t1) and disps rows t1-3, t1-2 are read.
+ *   t1 < 6, t1 - 1 >= n_frames or ht * wd == 0 is DBA_ERR_ARG, as is a report that is not the stream's block.
+ * dba_keyframe_flow_magnitude: delta.norm(dim=-1).mean() of dbaf/motion_filter.py:87: the mean over n_pixels (dx, dy)
+ *   pairs of sqrt(dx^2 + dy^2), in word DBA_KF_D (the other payload words are left as they are).  One fixed summation
+ *   order (lane-strided, wave sum, partials in wave order): bit-identical run to run.  DBA_F32: float throughout.
+ *   DBA_F16: torch's half semantics -- each norm in float, rounded to half; the halves summed in float; the mean rounded
+ *   to half.  delta aligned to one pair.  n_pixels == 0 is DBA_ERR_ARG; another dtype DBA_ERR_UNSUPPORTED.
+ * dba_keyframe_wait: returns once the block's completion word shows seq.  Every few thousand looks it asks the runtime
+ *   whether the block's stream has drained; drained without the word (a launch that failed) is DBA_ERR_HIP. */
+#define DBA_KF_D 0
+#define DBA_KF_WIN 1
+#define DBA_KF_CAM 2
+#define DBA_KF_MAT 9
+#define DBA_KF_SEQ 25
+#define DBA_KF_WORDS 26
+int dba_keyframe_report_words(void);
+int dba_keyframe_report(dba_stream_t stream, void **report, int *seq);
+int dba_keyframe_check(const float *poses, const float *disps, const float *intrinsics, int n_frames, int ht, int wd,
+                       int t1, float beta, void *report, int seq, dba_stream_t stream);
+int dba_keyframe_flow_magnitude(const void *delta, int dtype, int n_pixels, void *report, int seq, dba_stream_t stream);
+int dba_keyframe_wait(const void *report, int seq);
+
 #define DBA_PEER_TIMEOUT 1
 size_t dba_peer_exchange_bytes(size_t max_doubles);
 int dba_peer_exchange_create(size_t bytes, void **region, unsigned char *handle64);
