@@ -152,6 +152,8 @@ SYMBOLS = {
     "dba_move_rows": (c_int, [ctypes.POINTER(RowJob), c_int, _P]),
     "dba_shift_rows": (c_int, [ctypes.POINTER(_P), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), c_int,
                                ctypes.c_int64, _P]),
+    "dba_roll_rows": (c_int, [ctypes.POINTER(_P), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), c_int,
+                              ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(_P), ctypes.POINTER(ctypes.c_int64), c_int, _P]),
     "dba_add_factors_plan": (c_int, [_P, _P, _P, c_int, _P, _P, c_int, _P, _P, c_int] + [c_int] * 4 + [_P, _P, _P, _P]),
     "dba_add_factors_payload": (c_int, [ctypes.POINTER(AfJob), c_int, ctypes.POINTER(AfGeometry), _P]),
     "dba_update_inputs_edges": (c_int, [_P, _P, c_int, _P, _P, c_int, _P, c_int, c_int, ctypes.c_int64, ctypes.c_int64,

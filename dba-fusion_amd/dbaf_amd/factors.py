@@ -370,8 +370,10 @@ def rm_keyframe(graph, ix):
 def shift_edges(graph, roll):
     """The edge-list statements of DBAFusionFrontend.__rollup (dbaf/dbaf_frontend.py:106-118): ii, jj, ii_bad, jj_bad
     minus roll; ii_inac, jj_inac minus roll and, with target_inac / weight_inac, without the edges where either went
-    negative.  Only the inactive lists are compacted, as in the reference.  The torch.roll of the video buffers
-    (:92-105), the counters (:89-91, :120-123) and the GTSAM re-keying (:124-152) stay the caller's.
+    negative.  Only the inactive lists are compacted, as in the reference.  The rotation of the video buffers
+    (:93-105) with the video's counters and current edge lists (:119-122) is dbaf_amd.rollup.rollup_video, and
+    dbaf_amd.rollup.rollup does both; t1 and count (:91-92), the GTSAM re-keying (:123-140) and the video.state
+    slices (:142-151) stay the caller's.
     Returns dict(kept_inactive, dropped_inactive, mover_launches)."""
     op = "shift_edges"
     roll = int(roll)

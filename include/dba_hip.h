@@ -690,6 +690,26 @@ int dba_move_rows(const dba_row_job *jobs_host, int n_jobs, dba_stream_t stream)
 int dba_shift_rows(void *const *bases_host, const int64_t *row_bytes_host, const int64_t *rows_host, int n_bufs,
                    int64_t ix, dba_stream_t stream);
 
+/* ---- window rollup (csrc/rollup.hip) ----------------------------------------------------------------------------------
+ * The torch.roll(x, -roll, 0) statements of DBAFusionFrontend.__rollup over the video buffers
+ * (dbaf/dbaf_frontend.py:94-105) IN PLACE, and the `-= roll` of video.cur_ii / cur_jj (:121-122), in ONE launch with no
+ * scratch buffer and no host read.  Up to DBA_MAX_SHIFT_BUFS buffers bases[k] of rows[k] rows of row_bytes[k] bytes, any
+ * dtype and row size; up to DBA_MAX_ROLL_LISTS device int64 lists lists[k] of list_lens[k] entries, each entry minus roll.
+ *   live < 0  (exact): every buffer becomes byte-identical to torch.roll(x, -roll, 0), new[r] = old[(r + roll) mod rows];
+ *     roll is any integer, reduced mod rows[k] per buffer as torch does; a buffer whose reduced roll is 0 (or that has no
+ *     rows or no bytes per row) is left out of the grid.
+ *   live >= 0 (live rows only): new[r] = old[r + roll] for 0 <= r < live - roll, every other row untouched; needs
+ *     0 <= roll <= live <= rows[k] for every buffer.  For the caller who knows that rows at or past `live` hold no frame.
+ * The rows r, r + roll, r + 2 roll, ... form gcd(rows, roll) disjoint cycles (live: min(roll, live - roll) open chains); a
+ * lane owns one such walk of one column element (the widest of 16 / 8 / 4 / 2 / 1 bytes dividing the base address and the
+ * row size) and is the only thread that touches those bytes, eight rows in flight before the first store.
+ * DBA_ERR_ARG before anything is enqueued: a null base with rows and bytes, a negative size, n_bufs > DBA_MAX_SHIFT_BUFS,
+ * n_lists > DBA_MAX_ROLL_LISTS, a live-mode range violation, a grid past 2^31 - 1 workgroups.  A call with nothing to move
+ * launches nothing.  The tables are host arrays, passed to the kernel by value.  Does not synchronise. */
+#define DBA_MAX_ROLL_LISTS 4
+int dba_roll_rows(void *const *bases_host, const int64_t *row_bytes_host, const int64_t *rows_host, int n_bufs, int64_t roll,
+                  int64_t live, int64_t *const *lists_host, const int64_t *list_lens_host, int n_lists, dba_stream_t stream);
+
 /* ---- adding edges (csrc/add_factors.hip) ----------------------------------------------------------------------------
  * CovisibleGraph.add_factors (dbaf/covisible_graph.py:102-149) in two launches around one host read.
  * dba_add_factors_plan: one launch, one workgroup, no atomics.  From the active lists (ii, jj, age)[n], the inactive
