@@ -171,6 +171,10 @@ SYMBOLS = {
     "dba_keyframe_check": (c_int, [_P] * 3 + [c_int] * 4 + [c_float, _P, c_int, _P]),
     "dba_keyframe_flow_magnitude": (c_int, [_P, c_int, c_int, _P, c_int, _P]),
     "dba_keyframe_wait": (c_int, [_P, c_int]),
+    "dba_gru_pack": (c_int, [ctypes.POINTER(_P), ctypes.POINTER(c_int), c_int, c_int, c_int, c_int, _P, _P]),
+    "dba_gru_context": (c_int, [_P, _P] + [c_int] * 4 + [_P, _P]),
+    "dba_gru_reset": (c_int, [_P, c_int, _P, _P, _P] + [c_int] * 4 + [_P]),
+    "dba_gru_blend": (c_int, [_P] * 5 + [c_int] * 4 + [_P, _P]),
 }
 
 _lib = None

@@ -1,0 +1,207 @@
+"""The update operator's ConvGRU on the MI355X: the reference's module (dbaf/modules/gru.py) with the body of its forward
+between the convolutions in four HIP launches (csrc/gru.hip).
+
+  pack(net, *inputs)                     torch.cat([net, torch.cat(inputs, 1)], 1), written once          (gru.py:20-21)
+  context(a, net)                        (sigmoid(a) * net).view(b, c, h*w).mean(-1).view(b, c, 1, 1)     (gru.py:24-25)
+  reset_(buf, cr, gr, net)               buf[:, :c] = sigmoid(cr + gr) * net, in place: buf becomes
+                                         cat([r*net, inp], 1) without r*net or the cat ever existing      (gru.py:28-29)
+  blend(cz, gz, cq, gq, net, out=None)   z = sigmoid(cz + gz); q = tanh(cq + gq); (1-z) * net + z * q     (gru.py:27-31)
+  ConvGRU(h_planes=128, i_planes=128)    the reference's constructor, submodule names and forward(net, *inputs): a
+                                         state dict of the reference loads unchanged
+
+Every statement of the reference yields a tensor of the input dtype (half under autocast); the kernels round to that dtype
+where a statement ends and compute in float32 in between, so a result differs from torch's statements only where a
+float32 transcendental or the float32 sum of the context lands on the other side of a rounding boundary.  The seven
+convolutions are the module's own nn.Conv2d calls (MIOpen), on the same contiguous inputs as the reference's.
+
+ConvGRU.forward takes the fused route when net and all inputs are contiguous device tensors of one dtype (float16 or
+float32), the convolutions answer in that dtype and nothing asks for a gradient (grad mode off, or neither an input nor a
+parameter requires one); otherwise it runs forward_statements, the reference's chain in plain torch ops.  CPU tensors
+raise.  Inputs are checked on the host without synchronising; work is enqueued on torch.cuda.current_stream(), memory
+comes from torch's allocator only, and a forward can be captured into a hipGraph.
+"""
+import ctypes
+
+import torch
+import torch.nn as nn
+
+from . import _lib
+
+MAX_SOURCES = 8
+_DTYPES = {torch.float32: _lib.DBA_F32, torch.float16: _lib.DBA_F16}
+
+
+def _require(cond, msg):
+    if not cond:
+        raise ValueError("gru (MI355X): " + msg)
+
+
+def _ptr(x):
+    return ctypes.c_void_p(x.data_ptr())
+
+
+def _planes(x, nm):
+    """x [n, c, *plane] -> (n, c, elements of a plane)"""
+    _require(isinstance(x, torch.Tensor), "%s must be a tensor" % nm)
+    _require(x.is_cuda, "%s must be a HIP device tensor; no CPU path" % nm)
+    _require(x.dtype in _DTYPES, "%s must be float16 or float32, got %s" % (nm, x.dtype))
+    _require(x.dim() >= 3, "%s must be [n, c, h, w] (or [n, c, hw]), got %s" % (nm, tuple(x.shape)))
+    _require(x.is_contiguous(), "%s must be contiguous" % nm)
+    _require(x.numel() > 0, "%s is empty: %s" % (nm, tuple(x.shape)))
+    return int(x.shape[0]), int(x.shape[1]), x[0, 0].numel()
+
+
+def _like(x, nm, ref, refnm):
+    _planes(x, nm)
+    _require(x.device == ref.device and x.dtype == ref.dtype,
+             "%s must be on %s's device in its dtype (%s, %s), got (%s, %s)" % (nm, refnm, ref.device, ref.dtype, x.device, x.dtype))
+    _require(x.shape == ref.shape, "%s must have %s's shape %s, got %s" % (nm, refnm, tuple(ref.shape), tuple(x.shape)))
+
+
+def _gate(g, nm, ref, n, c):
+    """a per-plane term, convX_glo(glo): [n, c, 1, 1] or any contiguous tensor of n * c elements"""
+    _require(isinstance(g, torch.Tensor) and g.is_cuda and g.device == ref.device,
+             "%s must be a HIP device tensor on %s; no CPU path" % (nm, ref.device))
+    _require(g.dtype == ref.dtype, "%s must be %s, got %s" % (nm, ref.dtype, g.dtype))
+    _require(g.is_contiguous() and g.numel() == n * c and g.dim() >= 2 and tuple(g.shape[:2]) == (n, c),
+             "%s must be a contiguous [%d, %d, 1, 1], got %s" % (nm, n, c, tuple(g.shape)))
+
+
+def _overlap(x, y):
+    a, b = x.data_ptr(), y.data_ptr()
+    return a < b + y.numel() * y.element_size() and b < a + x.numel() * x.element_size()
+
+
+def _stream(x):
+    return ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+
+
+def pack(net, *inputs):
+    """net [n, c0, h, w] and up to 7 inputs [n, c_k, h, w] -> [n, c0 + sum c_k, h, w]: torch.cat([net, torch.cat(inputs, 1)], 1)"""
+    srcs = (net,) + tuple(inputs)
+    _require(len(srcs) <= MAX_SOURCES, "at most %d sources (net and %d inputs), got %d" % (MAX_SOURCES, MAX_SOURCES - 1, len(srcs)))
+    n, _, hw = _planes(net, "net")
+    for k, x in enumerate(inputs):
+        _planes(x, "inputs[%d]" % k)
+        _require(x.device == net.device and x.dtype == net.dtype,
+                 "inputs[%d] must be on net's device in net's dtype (%s, %s), got (%s, %s)" % (k, net.device, net.dtype, x.device, x.dtype))
+        _require(x.shape[0] == n and x.shape[2:] == net.shape[2:],
+                 "inputs[%d] must be [%d, c, %s], got %s" % (k, n, ", ".join(str(s) for s in net.shape[2:]), tuple(x.shape)))
+    chans = [int(x.shape[1]) for x in srcs]
+    dst = torch.empty((n, sum(chans)) + tuple(net.shape[2:]), dtype=net.dtype, device=net.device)
+    ptrs = (ctypes.c_void_p * len(srcs))(*[x.data_ptr() for x in srcs])
+    cs = (ctypes.c_int * len(srcs))(*chans)
+    with torch.cuda.device(net.device):
+        _lib.check(_lib.load().dba_gru_pack(ptrs, cs, len(srcs), n, hw, _DTYPES[net.dtype], _ptr(dst), _stream(net)), "dba_gru_pack")
+    return dst
+
+
+def context(a, net):
+    """a = w(net), net [n, c, h, w] -> glo [n, c, 1, 1] = mean over the plane of sigmoid(a) * net, statement by statement"""
+    n, c, hw = _planes(net, "net")
+    _like(a, "a", net, "net")
+    glo = torch.empty((n, c) + (1,) * (net.dim() - 2), dtype=net.dtype, device=net.device)
+    with torch.cuda.device(net.device):
+        _lib.check(_lib.load().dba_gru_context(_ptr(a), _ptr(net), n, c, hw, _DTYPES[net.dtype], _ptr(glo), _stream(net)),
+                   "dba_gru_context")
+    return glo
+
+
+def reset_(buf, cr, gr, net):
+    """buf [n, C, h, w] (pack's result), cr = convr(buf), gr = convr_glo(glo) [n, c, 1, 1], net [n, c, h, w]:
+    buf[:, :c] = sigmoid(cr + gr) * net in place; channels c .. C-1 are left as they are.  Returns buf."""
+    n, c, hw = _planes(net, "net")
+    _like(cr, "cr", net, "net")
+    _gate(gr, "gr", net, n, c)
+    nb, cb, hwb = _planes(buf, "buf")
+    _require(buf.device == net.device and buf.dtype == net.dtype, "buf must be on net's device in net's dtype")
+    _require(nb == n and cb >= c and buf.shape[2:] == net.shape[2:],
+             "buf must be [%d, >= %d, %s], got %s" % (n, c, ", ".join(str(s) for s in net.shape[2:]), tuple(buf.shape)))
+    for x, nm in ((cr, "cr"), (gr, "gr"), (net, "net")):
+        _require(not _overlap(buf, x), "buf overlaps %s" % nm)
+    with torch.cuda.device(net.device):
+        _lib.check(_lib.load().dba_gru_reset(_ptr(buf), cb, _ptr(cr), _ptr(gr), _ptr(net), n, c, hw, _DTYPES[net.dtype],
+                                             _stream(net)), "dba_gru_reset")
+    return buf
+
+
+def blend(cz, gz, cq, gq, net, out=None):
+    """cz = convz(net_inp), cq = convq(cat([r*net, inp])) [n, c, h, w], gz, gq [n, c, 1, 1], net [n, c, h, w] -> the new net.
+    out: where to write it; net itself is allowed (in place), any other overlap with an input is not."""
+    n, c, hw = _planes(net, "net")
+    _like(cz, "cz", net, "net")
+    _like(cq, "cq", net, "net")
+    _gate(gz, "gz", net, n, c)
+    _gate(gq, "gq", net, n, c)
+    if out is None:
+        out = torch.empty_like(net)
+    else:
+        _like(out, "out", net, "net")
+        for x, nm in ((cz, "cz"), (gz, "gz"), (cq, "cq"), (gq, "gq")):
+            _require(not _overlap(out, x), "out overlaps %s" % nm)
+        _require(out.data_ptr() == net.data_ptr() or not _overlap(out, net), "out overlaps net without being net")
+    with torch.cuda.device(net.device):
+        _lib.check(_lib.load().dba_gru_blend(_ptr(cz), _ptr(gz), _ptr(cq), _ptr(gq), _ptr(net), n, c, hw, _DTYPES[net.dtype],
+                                             _ptr(out), _stream(net)), "dba_gru_blend")
+    return out
+
+
+# the seven convolutions: (submodule name, reads the inputs' channels next to the hidden state's, kernel size).  Names and
+# order are what a state dict of the reference's module carries.
+_CONVS = (("convz", True, 3), ("convr", True, 3), ("convq", True, 3), ("w", False, 1),
+          ("convz_glo", False, 1), ("convr_glo", False, 1), ("convq_glo", False, 1))
+
+
+class ConvGRU(nn.Module):
+    def __init__(self, h_planes=128, i_planes=128):
+        super().__init__()
+        for name, with_inputs, k in _CONVS:
+            setattr(self, name, nn.Conv2d(h_planes + (i_planes if with_inputs else 0), h_planes, k, padding=k // 2))
+
+    def _statements(self, net, inputs, a):
+        """glo = mean_hw(sigma(a) net); z = sigma(convz(x) + convz_glo(glo)), r likewise; q = tanh(convq([r net, inputs]) +
+        convq_glo(glo)); the new state (1 - z) net + z q -- one torch op per h(.) of include/dba_hip.h, a = w(net) given"""
+        n, c = net.shape[:2]
+        x = torch.cat((net,) + inputs, 1)
+        glo = (torch.sigmoid(a) * net).flatten(2).mean(2).reshape(n, c, 1, 1)
+        z = torch.sigmoid(self.convz(x) + self.convz_glo(glo))
+        r = torch.sigmoid(self.convr(x) + self.convr_glo(glo))
+        q = torch.tanh(self.convq(torch.cat((r * net,) + inputs, 1)) + self.convq_glo(glo))
+        keep = (1 - z) * net
+        return keep + z * q
+
+    def forward_statements(self, net, *inputs):
+        """the same update in plain torch ops, on any device: the route of everything the fused one does not take, and
+        what the fused route is compared with"""
+        return self._statements(net, tuple(inputs), self.w(net))
+
+    def _fusable(self, net, inputs):
+        xs = (net,) + tuple(inputs)
+        if net.dtype not in _DTYPES or net.dim() != 4 or len(xs) > MAX_SOURCES or net.numel() == 0:
+            return False
+        if any(x.dtype != net.dtype or x.device != net.device or not x.is_contiguous() or x.dim() != 4 or x.numel() == 0
+               or x.shape[0] != net.shape[0] or x.shape[2:] != net.shape[2:] for x in xs):
+            return False
+        if torch.is_grad_enabled() and (any(x.requires_grad for x in xs) or any(p.requires_grad for p in self.parameters())):
+            return False
+        return True
+
+    def forward(self, net, *inputs):
+        _require(len(inputs) >= 1, "forward needs net and at least one input")
+        for k, x in enumerate((net,) + tuple(inputs)):
+            _require(isinstance(x, torch.Tensor) and x.is_cuda, "%s must be a HIP device tensor; no CPU path"
+                     % ("net" if k == 0 else "inputs[%d]" % (k - 1)))
+        a = self.w(net)
+        # autocast may answer in another dtype than the inputs': then the statements' own promotion rules apply
+        if not self._fusable(net, inputs) or a.dtype != net.dtype:
+            return self._statements(net, tuple(inputs), a)
+
+        net_inp = pack(net, *inputs)
+        glo = context(a, net)
+
+        gz, gr, gq = self.convz_glo(glo), self.convr_glo(glo), self.convq_glo(glo)
+        cz = self.convz(net_inp)
+        cr = self.convr(net_inp)
+        reset_(net_inp, cr, gr, net)    # net_inp is cat([r*net, inp], 1) from here on; convz and convr are enqueued
+        cq = self.convq(net_inp)
+        return blend(cz, gz, cq, gq, net)

@@ -907,6 +907,33 @@ int dba_keyframe_check(const float *poses, const float *disps, const float *intr
 int dba_keyframe_flow_magnitude(const void *delta, int dtype, int n_pixels, void *report, int seq, dba_stream_t stream);
 int dba_keyframe_wait(const void *report, int seq);
 
+/* ---- ConvGRU glue (csrc/gru.hip) --------------------------------------------------------------------------------------
+ * The body of ConvGRU.forward (dbaf/modules/gru.py:19-32) around its seven convolutions, which stay with the caller, in
+ * four launches.  Tensors are [n, c, hw] of one dtype, DBA_F16 or DBA_F32 (another is DBA_ERR_UNSUPPORTED), aligned to an
+ * element.  Every statement of the reference yields a tensor of that dtype: h(.) below rounds to it, and the arithmetic
+ * between two roundings is float32, unfused.  Vectors of 16 bytes where the extents and the bases allow, else elements;
+ * no atomics, no host read, one fixed summation order.  Each call refuses, without a launch and with DBA_ERR_ARG: an extent
+ * <= 0, c * hw or n * c or the grid beyond 2^31 - 1, a null pointer, a destination that shares a byte with a source.
+ * dba_gru_pack: dst [n, sum c_k, hw] = the n_src <= DBA_GRU_MAX_SOURCES sources [n, c_k, hw] one behind the other along the
+ *   channels: inp = torch.cat(inputs, dim=1); net_inp = torch.cat([net, inp], dim=1) (:20-21) with srcs = (net, *inputs),
+ *   written once, byte-exact.  srcs and channels are HOST arrays of n_src entries.
+ * dba_gru_context: glo [n, c] = h(mean_hw(h(h(sigmoid(a)) * net))), a = w(net): glo = torch.sigmoid(self.w(net)) * net;
+ *   glo.view(b, c, h*w).mean(-1) (:24-25).  The sum is float32, times the float32 1 / hw as torch's mean.
+ * dba_gru_reset: buf [n, c_total, hw], channels [0, c) of every edge = h(h(sigmoid(h(cr + gr))) * net), cr = convr(net_inp)
+ *   [n, c, hw], gr = convr_glo(glo) [n, c]: r = torch.sigmoid(self.convr(net_inp) + self.convr_glo(glo)) and the first half of
+ *   torch.cat([r*net, inp], dim=1) (:28-29); channels [c, c_total) are not touched, so a buffer dba_gru_pack filled IS that
+ *   cat afterwards.  Every reader of buf's old content (convz, convr) must have been enqueued before.
+ * dba_gru_blend: out [n, c, hw] = h(h(h(1 - z) * net) + h(z * q)), z = h(sigmoid(h(cz + gz))), q = h(tanh(h(cq + gq))) (:27,
+ *   :29, :31); cz, cq [n, c, hw], gz, gq [n, c].  out == net is allowed (in place), any other overlap is not. */
+#define DBA_GRU_MAX_SOURCES 8
+int dba_gru_pack(const void *const *srcs, const int *channels, int n_src, int n, int hw, int dtype, void *dst,
+                 dba_stream_t stream);
+int dba_gru_context(const void *a, const void *net, int n, int c, int hw, int dtype, void *glo, dba_stream_t stream);
+int dba_gru_reset(void *buf, int c_total, const void *cr, const void *gr, const void *net, int n, int c, int hw, int dtype,
+                  dba_stream_t stream);
+int dba_gru_blend(const void *cz, const void *gz, const void *cq, const void *gq, const void *net, int n, int c, int hw,
+                  int dtype, void *out, dba_stream_t stream);
+
 #define DBA_PEER_TIMEOUT 1
 size_t dba_peer_exchange_bytes(size_t max_doubles);
 int dba_peer_exchange_create(size_t bytes, void **region, unsigned char *handle64);
