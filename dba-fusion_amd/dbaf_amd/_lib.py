@@ -12,7 +12,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DBA_HIP_LIB") or os.path.join(os.path.dirname(_HERE), "lib", "libdba_hip.so")
 
-DBA_F32, DBA_F16, DBA_F64 = 0, 1, 2
+DBA_F32, DBA_F16, DBA_F64, DBA_U8 = 0, 1, 2, 3
 _ERR = {-1: "DBA_ERR_ARG", -2: "DBA_ERR_WORKSPACE", -3: "DBA_ERR_HIP", -4: "DBA_ERR_UNSUPPORTED"}
 
 c_int, c_float, c_size_t, c_void_p = ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_void_p
@@ -175,6 +175,11 @@ SYMBOLS = {
     "dba_gru_context": (c_int, [_P, _P] + [c_int] * 4 + [_P, _P]),
     "dba_gru_reset": (c_int, [_P, c_int, _P, _P, _P] + [c_int] * 4 + [_P]),
     "dba_gru_blend": (c_int, [_P] * 5 + [c_int] * 4 + [_P, _P]),
+    "dba_enc_norm": (c_int, [_P, c_int, c_int, c_float, c_int, c_int, _P, _P, _P]),
+    "dba_enc_norm_skip": (c_int, [_P, _P, _P, c_int, c_int, c_float, c_int, _P, _P, _P, _P]),
+    "dba_enc_relu_skip": (c_int, [_P, _P, ctypes.c_longlong, c_int, _P, _P]),
+    "dba_enc_image": (c_int, [_P] + [c_int] * 5 + [_P, _P]),
+    "dba_enc_context_split": (c_int, [_P] + [c_int] * 5 + [_P, _P, _P]),
 }
 
 _lib = None

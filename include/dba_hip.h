@@ -34,7 +34,7 @@ enum {
   DBA_ERR_UNSUPPORTED = -4
 };
 
-enum { DBA_F32 = 0, DBA_F16 = 1, DBA_F64 = 2 }; /* element type selector for volume/corr buffers */
+enum { DBA_F32 = 0, DBA_F16 = 1, DBA_F64 = 2, DBA_U8 = 3 }; /* element type selector for volume/corr buffers; DBA_U8 only as dba_enc_image's src_dtype */
 
 typedef void *dba_stream_t;
 
@@ -933,6 +933,41 @@ int dba_gru_reset(void *buf, int c_total, const void *cr, const void *gr, const 
                   dba_stream_t stream);
 int dba_gru_blend(const void *cz, const void *gz, const void *cq, const void *gq, const void *net, int n, int c, int hw,
                   int dtype, void *out, dba_stream_t stream);
+
+/* ---- Encoder glue (csrc/extractor.hip) -----------------------------------------------------------------------------
+ * What the feature and context encoders (dbaf/modules/extractor.py:47-55, :183-198) and their caller
+ * (dbaf/motion_filter.py:29-30, :35-36, :64-65) run between the convolutions, which stay with the caller.  Tensors are
+ * [planes, hw] contiguous of one dtype, DBA_F16 or DBA_F32 (another is DBA_ERR_UNSUPPORTED), aligned to an element.  Every
+ * statement of the reference yields a tensor of that dtype: h(.) rounds to it, the arithmetic between two roundings is
+ * float32, unfused.  relu(x) = x > 0 ? x : (x != x ? x : 0): NaN goes through, as torch.relu lets it.  16-byte accesses
+ * where the extents and bases allow, else elements; no atomics, no host read, work on `stream` only.  Each call refuses,
+ * without a launch and with DBA_ERR_ARG: a null pointer, an extent <= 0, a grid beyond 2^31 - 1, an overlap not named below.
+ * norm(x)_i = (x_i - m) * r per plane: m = (sum x_i) / hw, r = 1 / sqrt(v + eps), v = (sum (x_i - m)^2) / hw over the values
+ *   the workgroup holds (not E[x^2] - m^2), float32.  One workgroup holds one plane in registers, so hw <= 65536 (beyond:
+ *   DBA_ERR_ARG).  A plane is n_items items, vectors of 16 bytes (hw * itemsize a multiple of 16 and every base aligned) or
+ *   elements; lanes = the power of two >= n_items / 2 (elements: n_items / 4) within [64, 1024]; lane t holds items t,
+ *   t + lanes, ... (per lane: the power of two >= n_items / lanes; elements: the next of 1, 4, 16, 64).  Summation order: a
+ *   lane adds its elements in index order, the 64 lanes of a wave fold (6 DPP steps), the wave totals are added in wave
+ *   order.  The same bits run to run.
+ * dba_enc_norm: out = h(relu?(norm(x))); out == x is allowed.  stats, optional, [planes, 2] float32: (m, r) as multiplied with.
+ * dba_enc_norm_skip: the tail of a residual block.  y = h(relu(norm(x))); s = skip as it is, or h(norm(d)) (the 1x1
+ *   downsample branch and its norm3); out = h(relu(h(s + y))).  Exactly one of skip / d is given.  out == x is allowed.
+ *   stats_d, optional and only with d: (m, r) of d's planes.
+ * dba_enc_relu_skip: out = h(relu(h(skip + h(relu(x))))) over count elements (norm_fn='none'); out == x is allowed.
+ * dba_enc_image: img [n, 3, H, W], src_dtype DBA_U8 or DBA_F32, BGR -> out [n, 3, H, W] of dtype, RGB:
+ *   out[:, c] = ((img[:, 2 - c] * (1/255)) - mean_c) / std_c in float32, mean = (0.485, 0.456, 0.406), std = (0.229, 0.224,
+ *   0.225) as float32; the product with the float32 reciprocal is what torch's `/ 255.0` runs on the device.  Rounded once
+ *   to half for DBA_F16.
+ * dba_enc_context_split: x [n, c_net + c_inp, hw] -> net [n, c_net, hw] = h(tanh(x[:, :c_net])) (the accurate tanhf),
+ *   inp [n, c_inp, hw] = h(relu(x[:, c_net:])). */
+int dba_enc_norm(const void *x, int planes, int hw, float eps, int relu, int dtype, void *out, float *stats,
+                 dba_stream_t stream);
+int dba_enc_norm_skip(const void *x, const void *skip, const void *d, int planes, int hw, float eps, int dtype, void *out,
+                      float *stats, float *stats_d, dba_stream_t stream);
+int dba_enc_relu_skip(const void *x, const void *skip, long long count, int dtype, void *out, dba_stream_t stream);
+int dba_enc_image(const void *img, int n, int H, int W, int src_dtype, int dtype, void *out, dba_stream_t stream);
+int dba_enc_context_split(const void *x, int n, int c_net, int c_inp, int hw, int dtype, void *net, void *inp,
+                          dba_stream_t stream);
 
 #define DBA_PEER_TIMEOUT 1
 size_t dba_peer_exchange_bytes(size_t max_doubles);
