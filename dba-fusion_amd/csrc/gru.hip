@@ -2,6 +2,7 @@
 // convolutions that stay with PyTorch / MIOpen:
 //
 //   dba_gru_pack     <- inp = torch.cat(inputs, 1); net_inp = torch.cat([net, inp], 1)        (dbaf/modules/gru.py:20-21)
+//   dba_gru_pack_relu   the same with torch.relu on chosen sources: the encoders' last ReLUs  (dbaf/droid_net.py:83, :89)
 //   dba_gru_context  <- glo = (sigmoid(w(net)) * net).view(b, c, h*w).mean(-1)                (:24-25)
 //   dba_gru_reset    <- r = sigmoid(convr(net_inp) + convr_glo(glo)); cat([r*net, inp], 1)    (:28-29)
 //   dba_gru_blend    <- z = sigmoid(..), q = tanh(..), net = (1-z) * net + z * q              (:27, :29, :31)
@@ -72,6 +73,77 @@ __global__ __launch_bounds__(MOVE_THREADS) void gru_pack_kernel(char *dst, PackT
     case 8: copy_chunk<uint64_t>(s, d, run / 8, chunk); break;
     case 4: copy_chunk<uint32_t>(s, d, run / 4, chunk); break;
     default: copy_chunk<uint16_t>(s, d, run / 2, chunk); break;
+  }
+}
+
+// pack with torch.relu on the marked sources: the same walk as gru_pack_kernel, in a kernel of its own so that the plain
+// copy keeps its registers.  The ReLU is taken on the bits (no conversion): an element is kept when its sign bit is clear
+// or it is a NaN, and becomes +0 otherwise, which is torch.relu byte for byte (NaN payloads go through, -0 -> +0).
+template <typename U>   // U: the unsigned integer of the element's size
+__device__ __forceinline__ U relu_bits(U u) {
+  constexpr U SIGN = (U)1 << (8 * sizeof(U) - 1);
+  constexpr U EXP = sizeof(U) == 2 ? (U)0x7c00 : (U)0x7f800000;
+  return (!(u & SIGN) || (U)(u & ~SIGN) > EXP) ? u : (U)0;
+}
+
+template <typename V, typename U>
+__device__ __forceinline__ void copy_chunk_relu(const char *s, char *d, long long n, unsigned chunk, bool relu) {
+  constexpr int PER = sizeof(V) / sizeof(U);
+  union Item {
+    V v;
+    U u[PER];
+  };
+  const V *sp = (const V *)s;
+  V *dp = (V *)d;
+  const long long e0 = (long long)chunk * MOVE_CHUNK + threadIdx.x;
+  Item it[MOVE_UNROLL];
+#pragma unroll
+  for (int u = 0; u < MOVE_UNROLL; u++)
+    if (e0 + u * MOVE_THREADS < n) it[u].v = sp[e0 + u * MOVE_THREADS];
+  if (relu) {
+#pragma unroll
+    for (int u = 0; u < MOVE_UNROLL; u++) {
+#pragma unroll
+      for (int j = 0; j < PER; j++) it[u].u[j] = relu_bits<U>(it[u].u[j]);
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < MOVE_UNROLL; u++)
+    if (e0 + u * MOVE_THREADS < n) dp[e0 + u * MOVE_THREADS] = it[u].v;
+}
+
+template <typename U>
+__global__ __launch_bounds__(MOVE_THREADS) void gru_pack_relu_kernel(char *dst, PackTable t, unsigned relu_mask) {
+  const unsigned e = blockIdx.x / t.chunks, local = blockIdx.x - e * t.chunks;
+  const char *src = t.src[0];
+  long long run = t.run[0], off = t.off[0];
+  unsigned start = 0;
+  bool relu = relu_mask & 1u;
+#pragma unroll
+  for (int k = 1; k < DBA_GRU_MAX_SOURCES; k++)
+    if (k < t.n_src && local >= t.chunk_start[k]) {
+      src = t.src[k];
+      run = t.run[k];
+      off = t.off[k];
+      start = t.chunk_start[k];
+      relu = (relu_mask >> k) & 1u;
+    }
+  const char *s = src + (long long)e * run;
+  char *d = dst + (long long)e * t.row_bytes + off;
+  const unsigned chunk = local - start;
+  if constexpr (sizeof(U) == 2) {
+    switch (t.width) {
+      case 16: copy_chunk_relu<u32x4, U>(s, d, run / 16, chunk, relu); break;
+      case 8: copy_chunk_relu<uint64_t, U>(s, d, run / 8, chunk, relu); break;
+      case 4: copy_chunk_relu<uint32_t, U>(s, d, run / 4, chunk, relu); break;
+      default: copy_chunk_relu<uint16_t, U>(s, d, run / 2, chunk, relu); break;
+    }
+  } else {
+    switch (t.width) {   // float elements: every run starts and ends on 4 bytes
+      case 16: copy_chunk_relu<u32x4, U>(s, d, run / 16, chunk, relu); break;
+      case 8: copy_chunk_relu<uint64_t, U>(s, d, run / 8, chunk, relu); break;
+      default: copy_chunk_relu<uint32_t, U>(s, d, run / 4, chunk, relu); break;
+    }
   }
 }
 
@@ -292,8 +364,9 @@ bool extents_ok(int n, int c, int hw) {
 
 extern "C" {
 
-int dba_gru_pack(const void *const *srcs, const int *channels, int n_src, int n, int hw, int dtype, void *dst,
-                 dba_stream_t stream) {
+// the checks and the table of a pack; with_relu: the kernel that applies the mask, else the plain copy
+static int pack_impl(const void *const *srcs, const int *channels, int n_src, int n, int hw, int dtype, void *dst, int with_relu,
+                     unsigned relu_mask, dba_stream_t stream) {
   const int isz = item_size(dtype);
   if (!isz) return DBA_ERR_UNSUPPORTED;
   if (!srcs || !channels || !dst || n_src < 1 || n_src > DBA_GRU_MAX_SOURCES || n <= 0 || hw <= 0) return DBA_ERR_ARG;
@@ -322,9 +395,26 @@ int dba_gru_pack(const void *const *srcs, const int *channels, int n_src, int n,
     if (chunks * (unsigned long long)n > (unsigned long long)INT32_MAX) return DBA_ERR_ARG;
   }
   t.chunks = (unsigned)chunks;
-  hipLaunchKernelGGL(gru_pack_kernel, dim3(t.chunks * (unsigned)n), dim3(MOVE_THREADS), 0, (hipStream_t)stream, (char *)dst, t);
+  const dim3 grid(t.chunks * (unsigned)n);
+  if (!with_relu)
+    hipLaunchKernelGGL(gru_pack_kernel, grid, dim3(MOVE_THREADS), 0, (hipStream_t)stream, (char *)dst, t);
+  else if (isz == 2)
+    hipLaunchKernelGGL(gru_pack_relu_kernel<uint16_t>, grid, dim3(MOVE_THREADS), 0, (hipStream_t)stream, (char *)dst, t, relu_mask);
+  else
+    hipLaunchKernelGGL(gru_pack_relu_kernel<uint32_t>, grid, dim3(MOVE_THREADS), 0, (hipStream_t)stream, (char *)dst, t, relu_mask);
   DBA_LAUNCH_CHECK();
   return DBA_OK;
+}
+
+int dba_gru_pack(const void *const *srcs, const int *channels, int n_src, int n, int hw, int dtype, void *dst,
+                 dba_stream_t stream) {
+  return pack_impl(srcs, channels, n_src, n, hw, dtype, dst, 0, 0u, stream);
+}
+
+int dba_gru_pack_relu(const void *const *srcs, const int *channels, int n_src, int n, int hw, int dtype, void *dst,
+                      unsigned relu_mask, dba_stream_t stream) {
+  if (n_src >= 1 && n_src <= DBA_GRU_MAX_SOURCES && (relu_mask >> n_src)) return DBA_ERR_ARG;   // a bit without a source
+  return pack_impl(srcs, channels, n_src, n, hw, dtype, dst, 1, relu_mask, stream);
 }
 
 int dba_gru_context(const void *a, const void *net, int n, int c, int hw, int dtype, void *glo, dba_stream_t stream) {

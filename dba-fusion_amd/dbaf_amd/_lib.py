@@ -49,6 +49,12 @@ class AfGeometry(ctypes.Structure):
                 ("n_frames", c_int), ("ht", c_int), ("wd", c_int), ("reserved", c_int)]
 
 
+class UpdHead(ctypes.Structure):
+    """dba_upd_head_t of include/dba_hip.h"""
+    _fields_ = [("x", c_void_p), ("weight", c_void_p), ("bias", c_void_p), ("out", c_void_p), ("sum", c_void_p),
+                ("k", c_int), ("relu_in", c_int), ("act", c_int), ("scale", c_float)]
+
+
 # every exported symbol of include/dba_hip.h with its (restype, argtypes); pointers are void*
 _P = c_void_p
 SYMBOLS = {
@@ -172,6 +178,7 @@ SYMBOLS = {
     "dba_keyframe_flow_magnitude": (c_int, [_P, c_int, c_int, _P, c_int, _P]),
     "dba_keyframe_wait": (c_int, [_P, c_int]),
     "dba_gru_pack": (c_int, [ctypes.POINTER(_P), ctypes.POINTER(c_int), c_int, c_int, c_int, c_int, _P, _P]),
+    "dba_gru_pack_relu": (c_int, [ctypes.POINTER(_P), ctypes.POINTER(c_int), c_int, c_int, c_int, c_int, _P, ctypes.c_uint, _P]),
     "dba_gru_context": (c_int, [_P, _P] + [c_int] * 4 + [_P, _P]),
     "dba_gru_reset": (c_int, [_P, c_int, _P, _P, _P] + [c_int] * 4 + [_P]),
     "dba_gru_blend": (c_int, [_P] * 5 + [c_int] * 4 + [_P, _P]),
@@ -180,6 +187,8 @@ SYMBOLS = {
     "dba_enc_relu_skip": (c_int, [_P, _P, ctypes.c_longlong, c_int, _P, _P]),
     "dba_enc_image": (c_int, [_P] + [c_int] * 5 + [_P, _P]),
     "dba_enc_context_split": (c_int, [_P] + [c_int] * 5 + [_P, _P, _P]),
+    "dba_upd_heads": (c_int, [ctypes.POINTER(UpdHead)] + [c_int] * 6 + [_P]),
+    "dba_upd_heads_tile": (c_int, [ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
 }
 
 _lib = None

@@ -1,13 +1,15 @@
 """The update operator's ConvGRU on the MI355X: the reference's module (dbaf/modules/gru.py) with the body of its forward
 between the convolutions in four HIP launches (csrc/gru.hip).
 
-  pack(net, *inputs)                     torch.cat([net, torch.cat(inputs, 1)], 1), written once          (gru.py:20-21)
+  pack(net, *inputs, relu=())            torch.cat([net, torch.cat(inputs, 1)], 1), written once          (gru.py:20-21);
+                                         relu: torch.relu on the marked sources while they are copied
   context(a, net)                        (sigmoid(a) * net).view(b, c, h*w).mean(-1).view(b, c, 1, 1)     (gru.py:24-25)
   reset_(buf, cr, gr, net)               buf[:, :c] = sigmoid(cr + gr) * net, in place: buf becomes
                                          cat([r*net, inp], 1) without r*net or the cat ever existing      (gru.py:28-29)
   blend(cz, gz, cq, gq, net, out=None)   z = sigmoid(cz + gz); q = tanh(cq + gq); (1-z) * net + z * q     (gru.py:27-31)
   ConvGRU(h_planes=128, i_planes=128)    the reference's constructor, submodule names and forward(net, *inputs): a
-                                         state dict of the reference loads unchanged
+                                         state dict of the reference loads unchanged; forward_relu(net, inputs, relu) is
+                                         forward with the marked inputs still before their ReLU (dbaf_amd.update_op)
 
 Every statement of the reference yields a tensor of the input dtype (half under autocast); the kernels round to that dtype
 where a statement ends and compute in float32 in between, so a result differs from torch's statements only where a
@@ -76,10 +78,14 @@ def _stream(x):
     return ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
 
 
-def pack(net, *inputs):
-    """net [n, c0, h, w] and up to 7 inputs [n, c_k, h, w] -> [n, c0 + sum c_k, h, w]: torch.cat([net, torch.cat(inputs, 1)], 1)"""
+def pack(net, *inputs, relu=()):
+    """net [n, c0, h, w] and up to 7 inputs [n, c_k, h, w] -> [n, c0 + sum c_k, h, w]: torch.cat([net, torch.cat(inputs, 1)], 1).
+    relu: one flag per source (net first), or empty; a marked source goes through torch.relu while it is copied (the
+    encoders' last ReLUs, dbaf/droid_net.py:83, :89).  Empty, or no flag set: the plain copy, dba_gru_pack."""
     srcs = (net,) + tuple(inputs)
     _require(len(srcs) <= MAX_SOURCES, "at most %d sources (net and %d inputs), got %d" % (MAX_SOURCES, MAX_SOURCES - 1, len(srcs)))
+    relu = tuple(bool(f) for f in relu)
+    _require(len(relu) in (0, len(srcs)), "relu must be empty or one flag per source (%d), got %d" % (len(srcs), len(relu)))
     n, _, hw = _planes(net, "net")
     for k, x in enumerate(inputs):
         _planes(x, "inputs[%d]" % k)
@@ -91,8 +97,13 @@ def pack(net, *inputs):
     dst = torch.empty((n, sum(chans)) + tuple(net.shape[2:]), dtype=net.dtype, device=net.device)
     ptrs = (ctypes.c_void_p * len(srcs))(*[x.data_ptr() for x in srcs])
     cs = (ctypes.c_int * len(srcs))(*chans)
+    mask = sum(1 << k for k, f in enumerate(relu) if f)
     with torch.cuda.device(net.device):
-        _lib.check(_lib.load().dba_gru_pack(ptrs, cs, len(srcs), n, hw, _DTYPES[net.dtype], _ptr(dst), _stream(net)), "dba_gru_pack")
+        if mask:
+            _lib.check(_lib.load().dba_gru_pack_relu(ptrs, cs, len(srcs), n, hw, _DTYPES[net.dtype], _ptr(dst), mask, _stream(net)),
+                       "dba_gru_pack_relu")
+        else:
+            _lib.check(_lib.load().dba_gru_pack(ptrs, cs, len(srcs), n, hw, _DTYPES[net.dtype], _ptr(dst), _stream(net)), "dba_gru_pack")
     return dst
 
 
@@ -187,16 +198,28 @@ class ConvGRU(nn.Module):
         return True
 
     def forward(self, net, *inputs):
+        return self._forward(net, tuple(inputs), ())
+
+    def forward_relu(self, net, inputs, relu):
+        """forward(net, *inputs) with the inputs marked in `relu` (one flag per input) still BEFORE their ReLU: the fused route
+        applies it inside pack, the statement route as torch.relu.  An empty `relu` is forward."""
+        inputs, relu = tuple(inputs), tuple(bool(f) for f in relu)
+        _require(len(relu) in (0, len(inputs)), "relu must be empty or one flag per input (%d), got %d" % (len(inputs), len(relu)))
+        return self._forward(net, inputs, relu)
+
+    def _forward(self, net, inputs, relu):
         _require(len(inputs) >= 1, "forward needs net and at least one input")
-        for k, x in enumerate((net,) + tuple(inputs)):
+        for k, x in enumerate((net,) + inputs):
             _require(isinstance(x, torch.Tensor) and x.is_cuda, "%s must be a HIP device tensor; no CPU path"
                      % ("net" if k == 0 else "inputs[%d]" % (k - 1)))
         a = self.w(net)
         # autocast may answer in another dtype than the inputs': then the statements' own promotion rules apply
         if not self._fusable(net, inputs) or a.dtype != net.dtype:
-            return self._statements(net, tuple(inputs), a)
+            if any(relu):
+                inputs = tuple(torch.relu(x) if f else x for x, f in zip(inputs, relu))
+            return self._statements(net, inputs, a)
 
-        net_inp = pack(net, *inputs)
+        net_inp = pack(net, *inputs, relu=((False,) + relu) if any(relu) else ())
         glo = context(a, net)
 
         gz, gr, gq = self.convz_glo(glo), self.convr_glo(glo), self.convq_glo(glo)

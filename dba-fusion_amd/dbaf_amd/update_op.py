@@ -1,0 +1,304 @@
+"""The update operator on the MI355X: the reference's UpdateModule and GraphAgg (dbaf/droid_net.py:40-142) with everything
+around the ConvGRU that is not a convolution of 64 outputs or more in this project's own launches (csrc/update_op.hip,
+csrc/gru.hip).
+
+  heads(*specs)        the checked wrapper of dba_upd_heads: one or two 3x3 convolutions with one or two output channels in
+                       ONE launch, each with an optional ReLU on its input, its bias, and nothing / sigmoid / softplus-and-
+                       scale behind it, written as [n, ht, wd, k]
+  Head(...)            one head of such a call
+  clear_cast_cache(m)  forget the half copies of the small convolutions' parameters (after a write through `.data`)
+  GraphAgg()           the reference's constructors, submodule names, nn.Sequential indices and forward parameter lists: a
+  UpdateModule()       state dict of the reference loads unchanged.  GradientClip stays in place as a parameter-free module
+                       (the identity in forward)
+
+UpdateModule.forward, fused route: the two encoders run their convolutions and their FIRST ReLU as torch; their last ReLU
+is applied by the GRU's pack while it copies (ConvGRU.forward_relu); delta[0] and weight[0] run as torch, and ONE heads call
+reads their two outputs once: ReLU, the 128 -> 2 convolutions, the sigmoid and the [b, n, h, w, 2] layout.  GraphAgg's eta
+head is the same kernel with one output, softplus and the factor .01.  forward_statements is the reference's chain in plain
+torch ops, on any device.
+
+Every fused piece routes on its own facts, as ConvGRU._fusable does: contiguous device tensors of one dtype in {float16,
+float32}, the convolution answering in that dtype, nothing asking for a gradient; otherwise that piece runs the statements.
+One more fact for eta: torch's autocast runs softplus in float32, so under autocast the statements answer in float32 from
+a half convolution, and the piece runs them (the kernel rounds to the tensor dtype; it would lose those bits).  CPU tensors
+raise.  No host synchronisation on the upsample=False path (GraphAgg keeps torch.unique's host read), work is enqueued on
+torch.cuda.current_stream(), memory comes from torch's allocator only, and a forward can be captured into a hipGraph.
+"""
+import ctypes
+
+import torch
+import torch.nn as nn
+
+from . import _lib
+from .gru import ConvGRU
+
+ACTS = {"none": 0, "sigmoid": 1, "softplus": 2}   # DBA_UPD_ACT_* of include/dba_hip.h
+_DTYPES = {torch.float32: _lib.DBA_F32, torch.float16: _lib.DBA_F16}
+
+
+def _require(cond, msg):
+    if not cond:
+        raise ValueError("update_op (MI355X): " + msg)
+
+
+def _overlap(x, y):
+    a, b = x.data_ptr(), y.data_ptr()
+    return a < b + y.numel() * y.element_size() and b < a + x.numel() * x.element_size()
+
+
+class Head:
+    """one head of a heads() call.  x [n, c, ht, wd]; weight [k, c, 3, 3], k in {1, 2}; bias [k] or None; relu_in: x is
+    still before its ReLU; act: "none" | "sigmoid" | "softplus" (then out = scale * softplus(v), rounded after each);
+    out: where to write [n, ht, wd, k] (default: a new tensor); want_sum: also return the float32 s + b"""
+
+    def __init__(self, x, weight, bias=None, relu_in=False, act="none", scale=1.0, out=None, want_sum=False):
+        self.x, self.weight, self.bias, self.relu_in, self.act, self.scale = x, weight, bias, bool(relu_in), act, float(scale)
+        self.out, self.want_sum = out, bool(want_sum)
+
+
+def tile():
+    """(rows, cols) of the kernel's tile"""
+    r, c = ctypes.c_int(), ctypes.c_int()
+    _lib.check(_lib.load().dba_upd_heads_tile(ctypes.byref(r), ctypes.byref(c)), "dba_upd_heads_tile")
+    return r.value, c.value
+
+
+def heads(*specs):
+    """one launch for one or two Heads that share n, c, ht, wd, device and dtype -> a list, per head `out` [n, ht, wd, k], or
+    (out, sum) where want_sum.  Raises ValueError before anything is enqueued."""
+    _require(1 <= len(specs) <= 2 and all(isinstance(h, Head) for h in specs), "one or two Head specs, got %d" % len(specs))
+    x0 = specs[0].x
+    _require(isinstance(x0, torch.Tensor) and x0.is_cuda, "heads[0].x must be a HIP device tensor; no CPU path")
+    _require(x0.dtype in _DTYPES, "heads[0].x must be float16 or float32, got %s" % x0.dtype)
+    _require(x0.dim() == 4 and x0.numel() > 0, "heads[0].x must be a non-empty [n, c, ht, wd], got %s" % (tuple(x0.shape),))
+    n, c, ht, wd = (int(s) for s in x0.shape)
+    _require(n * c * ht * wd < 2 ** 31, "n * c * ht * wd must stay below 2^31, got %d" % (n * c * ht * wd))
+    arr = (_lib.UpdHead * len(specs))()
+    results, written, read = [], [], []
+    for i, h in enumerate(specs):
+        nm = "heads[%d]" % i
+        _require(h.act in ACTS, "%s.act must be one of %s, got %r" % (nm, sorted(ACTS), h.act))
+        for t, what in ((h.x, "x"), (h.weight, "weight")) + (((h.bias, "bias"),) if h.bias is not None else ()):
+            _require(isinstance(t, torch.Tensor) and t.is_cuda, "%s.%s must be a HIP device tensor; no CPU path" % (nm, what))
+            _require(t.device == x0.device and t.dtype == x0.dtype,
+                     "%s.%s must be on %s in %s, got (%s, %s)" % (nm, what, x0.device, x0.dtype, t.device, t.dtype))
+            _require(t.is_contiguous(), "%s.%s must be contiguous" % (nm, what))
+            read.append((t, "%s.%s" % (nm, what)))
+        _require(tuple(h.x.shape) == (n, c, ht, wd), "%s.x must be %s as heads[0].x, got %s" % (nm, (n, c, ht, wd), tuple(h.x.shape)))
+        _require(h.weight.dim() == 4 and h.weight.shape[0] in (1, 2) and tuple(h.weight.shape[1:]) == (c, 3, 3),
+                 "%s.weight must be [1 or 2, %d, 3, 3], got %s" % (nm, c, tuple(h.weight.shape)))
+        k = int(h.weight.shape[0])
+        _require(h.bias is None or tuple(h.bias.shape) == (k,), "%s.bias must be [%d]" % (nm, k))
+        if h.out is None:
+            out = torch.empty((n, ht, wd, k), dtype=x0.dtype, device=x0.device)
+        else:
+            out = h.out
+            _require(isinstance(out, torch.Tensor) and out.is_cuda and out.device == x0.device and out.dtype == x0.dtype
+                     and out.is_contiguous() and tuple(out.shape) == (n, ht, wd, k),
+                     "%s.out must be a contiguous [%d, %d, %d, %d] of %s on %s" % (nm, n, ht, wd, k, x0.dtype, x0.device))
+        s = torch.empty((n, ht, wd, k), dtype=torch.float32, device=x0.device) if h.want_sum else None
+        written.append((out, nm + ".out"))
+        arr[i] = _lib.UpdHead(h.x.data_ptr(), h.weight.data_ptr(), h.bias.data_ptr() if h.bias is not None else None,
+                              out.data_ptr(), s.data_ptr() if s is not None else None, k, int(h.relu_in), ACTS[h.act], h.scale)
+        results.append((out, s) if h.want_sum else out)
+    for i, (o, onm) in enumerate(written):
+        for t, tnm in read:
+            _require(not _overlap(o, t), "%s overlaps %s" % (onm, tnm))
+        for o2, onm2 in written[i + 1:]:
+            _require(not _overlap(o, o2), "%s overlaps %s" % (onm, onm2))
+    stream = ctypes.c_void_p(torch.cuda.current_stream(x0.device).cuda_stream)
+    with torch.cuda.device(x0.device):
+        _lib.check(_lib.load().dba_upd_heads(arr, len(specs), n, c, ht, wd, _DTYPES[x0.dtype], stream), "dba_upd_heads")
+    return results
+
+
+class _ClipGrad(torch.autograd.Function):
+    """the identity; on the way back a gradient entry that is NaN or larger than 0.01 in magnitude becomes 0"""
+
+    @staticmethod
+    def forward(ctx, x):
+        return x
+
+    @staticmethod
+    def backward(ctx, g):
+        return g.masked_fill((g.abs() > 0.01) | torch.isnan(g), 0.0)
+
+
+class GradientClip(nn.Module):
+    """parameter-free; the identity in forward"""
+
+    def forward(self, x):
+        return _ClipGrad.apply(x)
+
+
+def _asks_gradient(module, tensors):
+    return torch.is_grad_enabled() and (any(t.requires_grad for t in tensors) or any(p.requires_grad for p in module.parameters()))
+
+
+def _dense(t):
+    """a contiguous non-empty [n, c, ht, wd] device tensor of a supported dtype"""
+    return t.is_cuda and t.dtype in _DTYPES and t.dim() == 4 and t.is_contiguous() and t.numel() > 0 and t.numel() < 2 ** 31
+
+
+def _head_fusable(module, conv, x):
+    """x: what the head's 3x3 convolution `conv` would read"""
+    if not _dense(x) or _asks_gradient(module, (x,)):
+        return False
+    want = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled() else conv.weight.dtype
+    return want == x.dtype and conv.weight.is_cuda and conv.weight.device == x.device
+
+
+def _params(conv, dtype):
+    """the convolution's weight and bias as the kernel reads them: contiguous, in x's dtype.  Under autocast that is a cast
+    of the float32 parameters; it is made once and kept on the convolution (the stand-in for autocast's own weight cache,
+    which lives only inside one autocast region).  The kept copy is replaced when a parameter is replaced, moved or
+    written in place (its _version changes: optimizer steps, load_state_dict, copy_ under no_grad).  A write through
+    `p.data` changes neither: after one, call clear_cast_cache(module).  During a stream capture nothing is kept: a copy made
+    there would live in the graph's private pool, so the cast is recorded into the graph (it then follows the parameters on
+    every replay) unless an eager call has made the copy before."""
+    w, b = conv.weight, conv.bias
+    if w.dtype == dtype and w.is_contiguous():
+        return w.detach(), (b.detach() if b is not None else None)
+    key = (dtype, w.data_ptr(), w._version, None if b is None else (b.data_ptr(), b._version))
+    kept = conv.__dict__.get("_dba_cast")
+    if kept is None or kept[0] != key:
+        kept = (key, w.detach().to(dtype).contiguous(), None if b is None else b.detach().to(dtype).contiguous())
+        if not torch.cuda.is_current_stream_capturing():
+            conv.__dict__["_dba_cast"] = kept
+    return kept[1], kept[2]
+
+
+def clear_cast_cache(module):
+    """forget the half copies of parameters kept by the fused heads of `module` and its submodules (needed only after a
+    parameter was written through `.data`)"""
+    for m in module.modules():
+        m.__dict__.pop("_dba_cast", None)
+
+
+def _scatter_mean_plain(src, ix, dim_size):
+    """scatter_mean(src [b, n, ...], ix [n], dim=1) in plain torch ops, on any device"""
+    out = torch.zeros((src.shape[0], dim_size) + tuple(src.shape[2:]), dtype=src.dtype, device=src.device)
+    out.index_add_(1, ix, src)
+    count = torch.zeros(dim_size, dtype=src.dtype, device=src.device).index_add_(0, ix, torch.ones_like(ix, dtype=src.dtype))
+    return out / count.clamp(min=1).view(1, -1, *([1] * (src.dim() - 2)))
+
+
+class GraphAgg(nn.Module):
+    def __init__(self):
+        super().__init__()
+        self.conv1 = nn.Conv2d(128, 128, 3, padding=1)
+        self.conv2 = nn.Conv2d(128, 128, 3, padding=1)
+        self.relu = nn.ReLU(inplace=True)
+        self.eta = nn.Sequential(nn.Conv2d(128, 1, 3, padding=1), GradientClip(), nn.Softplus())
+        self.upmask = nn.Sequential(nn.Conv2d(128, 8 * 8 * 9, 1, padding=0))
+
+    def _aggregate(self, net, ii, plain):
+        batch, num, ch, ht, wd = net.shape
+        net = net.view(batch * num, ch, ht, wd)
+        uniq, ix = torch.unique(ii, return_inverse=True)
+        net = self.relu(self.conv1(net))
+        net = net.view(batch, num, 128, ht, wd)
+        if plain:
+            net = _scatter_mean_plain(net, ix, int(uniq.numel()))
+        else:
+            from torch_scatter import scatter_mean
+            net = scatter_mean(net, ix, dim=1)
+        net = net.view(-1, 128, ht, wd)
+        return self.relu(self.conv2(net)), batch, ht, wd
+
+    def forward_statements(self, net, ii):
+        """the reference's chain in plain torch ops, on any device"""
+        net, batch, ht, wd = self._aggregate(net, ii, True)
+        eta = self.eta(net).view(batch, -1, ht, wd)
+        upmask = self.upmask(net).view(batch, -1, 8 * 8 * 9, ht, wd)
+        return .01 * eta, upmask
+
+    def forward(self, net, ii):
+        _require(isinstance(net, torch.Tensor) and net.is_cuda, "net must be a HIP device tensor; no CPU path")
+        if _asks_gradient(self, (net,)):
+            return self.forward_statements(net, ii)
+        net, batch, ht, wd = self._aggregate(net, ii, False)
+        # conv2's ReLU stays a torch launch (upmask's convolution reads it too), so eta reads it with relu_in off.
+        # Under autocast torch's softplus answers in float32: then the statements run.
+        if _head_fusable(self, self.eta[0], net) and not torch.is_autocast_enabled():
+            w, b = _params(self.eta[0], net.dtype)
+            eta = heads(Head(net, w, b, relu_in=False, act="softplus", scale=.01))[0].view(batch, -1, ht, wd)
+        else:
+            eta = .01 * self.eta(net).view(batch, -1, ht, wd)
+        upmask = self.upmask(net).view(batch, -1, 8 * 8 * 9, ht, wd)
+        return eta, upmask
+
+
+class UpdateModule(nn.Module):
+    def __init__(self):
+        super().__init__()
+        cor_planes = 4 * (2 * 3 + 1) ** 2
+        self.corr_encoder = nn.Sequential(nn.Conv2d(cor_planes, 128, 1, padding=0), nn.ReLU(inplace=True),
+                                          nn.Conv2d(128, 128, 3, padding=1), nn.ReLU(inplace=True))
+        self.flow_encoder = nn.Sequential(nn.Conv2d(4, 128, 7, padding=3), nn.ReLU(inplace=True),
+                                          nn.Conv2d(128, 64, 3, padding=1), nn.ReLU(inplace=True))
+        self.weight = nn.Sequential(nn.Conv2d(128, 128, 3, padding=1), nn.ReLU(inplace=True), nn.Conv2d(128, 2, 3, padding=1),
+                                    GradientClip(), nn.Sigmoid())
+        self.delta = nn.Sequential(nn.Conv2d(128, 128, 3, padding=1), nn.ReLU(inplace=True), nn.Conv2d(128, 2, 3, padding=1),
+                                   GradientClip())
+        self.gru = ConvGRU(128, 128 + 128 + 64)
+        self.agg = GraphAgg()
+
+    @staticmethod
+    def _flat(net, inp, corr, flow):
+        batch, num, ch, ht, wd = net.shape
+        if flow is None:
+            flow = torch.zeros(batch, num, 4, ht, wd, device=net.device)
+        shape = (batch * num, -1, ht, wd)
+        return (net.view(shape), inp.view(shape), corr.view(shape), flow.view(shape)), (batch, num, -1, ht, wd)
+
+    @staticmethod
+    def _result(net, delta, weight, agg, ii, upsample):
+        if ii is None:
+            return net, delta, weight
+        if upsample:
+            eta, upmask = agg(net, ii.to(net.device))
+            return net, delta, weight, eta, upmask
+        return net, delta, weight, None, None
+
+    def forward_statements(self, net, inp, corr, flow=None, ii=None, jj=None, upsample=False):
+        """the reference's chain in plain torch ops, on any device"""
+        (net, inp, corr, flow), dim = self._flat(net, inp, corr, flow)
+        corr = self.corr_encoder(corr)
+        flow = self.flow_encoder(flow)
+        net = self.gru.forward_statements(net, inp, corr, flow)
+        delta = self.delta(net).view(*dim)
+        weight = self.weight(net).view(*dim)
+        delta = delta.permute(0, 1, 3, 4, 2)[..., :2].contiguous()
+        weight = weight.permute(0, 1, 3, 4, 2)[..., :2].contiguous()
+        return self._result(net.view(*dim), delta, weight, self.agg.forward_statements, ii, upsample)
+
+    def forward(self, net, inp, corr, flow=None, ii=None, jj=None, upsample=False):
+        for t, nm in ((net, "net"), (inp, "inp"), (corr, "corr")) + (((flow, "flow"),) if flow is not None else ()):
+            _require(isinstance(t, torch.Tensor) and t.is_cuda, "%s must be a HIP device tensor; no CPU path" % nm)
+        (net, inp, corr, flow), dim = self._flat(net, inp, corr, flow)
+        asks = _asks_gradient(self, (net, inp, corr, flow))
+
+        # the encoders without their last ReLU; the GRU's pack applies it while it copies
+        ce, fe = self.corr_encoder, self.flow_encoder
+        corr = ce[2](ce[1](ce[0](corr)))
+        flow = fe[2](fe[1](fe[0](flow)))
+        if (not asks and _dense(net) and corr.dtype == net.dtype and flow.dtype == net.dtype and inp.dtype == net.dtype
+                and inp.is_contiguous()):
+            net = self.gru.forward_relu(net, (inp, corr, flow), relu=(False, True, True))
+        else:
+            net = self.gru(net, inp, ce[3](corr), fe[3](flow))
+
+        # the heads: the two first convolutions as torch, everything behind them in one launch
+        hd, hw = self.delta[0](net), self.weight[0](net)
+        if (not asks and hd.dtype == hw.dtype and _head_fusable(self, self.delta[2], hd) and _head_fusable(self, self.weight[2], hw)
+                and _dense(hw)):
+            wd_, bd = _params(self.delta[2], hd.dtype)
+            ww, bw = _params(self.weight[2], hw.dtype)
+            delta, weight = heads(Head(hd, wd_, bd, relu_in=True, act="none"), Head(hw, ww, bw, relu_in=True, act="sigmoid"))
+            delta, weight = delta.view(dim[0], dim[1], dim[3], dim[4], 2), weight.view(dim[0], dim[1], dim[3], dim[4], 2)
+        else:
+            d, w = self.delta, self.weight
+            delta = d[3](d[2](d[1](hd))).view(*dim).permute(0, 1, 3, 4, 2)[..., :2].contiguous()
+            weight = w[4](w[3](w[2](w[1](hw)))).view(*dim).permute(0, 1, 3, 4, 2)[..., :2].contiguous()
+        return self._result(net.view(*dim), delta, weight, self.agg, ii, upsample)

@@ -928,6 +928,11 @@ int dba_keyframe_wait(const void *report, int seq);
 #define DBA_GRU_MAX_SOURCES 8
 int dba_gru_pack(const void *const *srcs, const int *channels, int n_src, int n, int hw, int dtype, void *dst,
                  dba_stream_t stream);
+/* dba_gru_pack with torch.relu applied to the sources whose bit of relu_mask is set (bit k: srcs[k]) while they are copied:
+ * byte-equal to torch.cat of the sources with torch.relu on the marked ones (NaN goes through with its payload, -0 and
+ * everything negative become +0).  A launch of its own kernel; relu_mask == 0 copies as dba_gru_pack does. */
+int dba_gru_pack_relu(const void *const *srcs, const int *channels, int n_src, int n, int hw, int dtype, void *dst,
+                      unsigned relu_mask, dba_stream_t stream);
 int dba_gru_context(const void *a, const void *net, int n, int c, int hw, int dtype, void *glo, dba_stream_t stream);
 int dba_gru_reset(void *buf, int c_total, const void *cr, const void *gr, const void *net, int n, int c, int hw, int dtype,
                   dba_stream_t stream);
@@ -968,6 +973,43 @@ int dba_enc_relu_skip(const void *x, const void *skip, long long count, int dtyp
 int dba_enc_image(const void *img, int n, int H, int W, int src_dtype, int dtype, void *out, dba_stream_t stream);
 int dba_enc_context_split(const void *x, int n, int c_net, int c_inp, int hw, int dtype, void *net, void *inp,
                           dba_stream_t stream);
+
+/* ---- Update operator heads (csrc/update_op.hip) ---------------------------------------------------------------------
+ * The 3x3 convolutions with one or two outputs of the update operator (dbaf/droid_net.py:47-50, :91-102) with what runs
+ * around them (:68, :71, :124-128), every head of a call in one launch.  All heads of a call share n, c, ht, wd and the
+ * dtype, DBA_F16 or DBA_F32 (another is DBA_ERR_UNSUPPORTED); tensors are contiguous and aligned to an element.  h(.)
+ * rounds to the dtype.  Per head:
+ *   s   = the float32 sum over (c, ky, kx) of relu?(x)[c, y + ky - 1, x + kx - 1] * w[o, c, ky, kx], zero padding of one
+ *         pixel.  SUMMATION ORDER, two levels: per pixel and output, every chunk of four channels (4 j .. 4 j + 3, the
+ *         last one possibly short) has its own sum, started at +0, its terms added one by one with c ascending, within
+ *         a channel ky ascending, within a row kx ascending (the order of w's memory), a padded tap as +0 * w; the chunk
+ *         sums are then added one by one in chunk order to an accumulator started at +0.  Product and addition round
+ *         separately (in half every product is exact in float32, only the additions round).  No atomics, no sum across
+ *         lanes: the same bits run to run, on both staging routes.
+ *   v   = h(s + b), b = bias[o] or 0; `sum`, when given, receives the float32 s + b that v was rounded from
+ *   out = v (DBA_UPD_ACT_NONE) | h(1 / (1 + expf(-v))) (_SIGMOID) | h(scale * h(softplus(v))) (_SOFTPLUS, torch's: v > 20 ?
+ *         v : log1pf(expf(v))); expf, log1pf and the division are the accurate library forms
+ *   relu(x) = x > 0 ? x : (x != x ? x : 0): NaN goes through, -0 becomes +0.  GradientClip is the identity in forward.
+ * out is [n, ht, wd, k]: the permute(..)[..., :k].contiguous() of the reference is the store, a pixel's two outputs as
+ * one pair.  Tile: dba_upd_heads_tile's rows x cols pixels of one edge per workgroup, all channels; x is staged through LDS
+ * in 16-byte vectors when hw * itemsize is a multiple of 16, every x is on a 16-byte boundary and wd <= cols, else element
+ * by element.  Refused without a launch, DBA_ERR_ARG: an extent <= 0, k outside {1, 2}, n_heads outside {1, 2}, an unknown
+ * act, a null x / weight / out, a pointer off its element size, a grid or n * c * ht * wd beyond 2^31 - 1, an out or sum
+ * that shares a byte with any input of the call, with another head's out or sum, or with each other.  `heads` is a HOST array. */
+enum { DBA_UPD_ACT_NONE = 0, DBA_UPD_ACT_SIGMOID = 1, DBA_UPD_ACT_SOFTPLUS = 2 };
+typedef struct {
+  const void *x;      /* [n, c, ht, wd]  the head's hidden tensor (pre-ReLU when relu_in) */
+  const void *weight; /* [k, c, 3, 3]    same dtype as x */
+  const void *bias;   /* [k] or NULL */
+  void *out;          /* [n, ht, wd, k]  same dtype */
+  float *sum;         /* optional [n, ht, wd, k] float32: s + b as it was rounded from */
+  int k;              /* 1 or 2 */
+  int relu_in;        /* apply ReLU to x as it is read */
+  int act;            /* DBA_UPD_ACT_NONE | _SIGMOID | _SOFTPLUS */
+  float scale;        /* _SOFTPLUS only: out = h(scale * h(softplus(v))) */
+} dba_upd_head_t;
+int dba_upd_heads(const dba_upd_head_t *heads, int n_heads, int n, int c, int ht, int wd, int dtype, dba_stream_t stream);
+int dba_upd_heads_tile(int *rows, int *cols); /* the kernel's tile extents, for the tests */
 
 #define DBA_PEER_TIMEOUT 1
 size_t dba_peer_exchange_bytes(size_t max_doubles);
