@@ -28,6 +28,7 @@ void set_last_error(const char *what, hipError_t e) {
 }
 
 // The environment switches of this file, all read once per process ("Environment switches of libdba_hip.so").
+constexpr bool STAGE0_FOLD_DEFAULT = true;
 struct BaEnv {
   static int num(const char *name) { const char *e = getenv(name); return e ? atoi(e) : 0; }
   static bool is(const char *name, const char *prefix) { const char *e = getenv(name); return e && !strncmp(e, prefix, strlen(prefix)); }
@@ -51,6 +52,8 @@ struct BaEnv {
   // precision class, half the pipe time): DBA_SCHUR_MFMA=f64|f32
   bool gram_f32 = getenv("DBA_SCHUR_MFMA") ? is("DBA_SCHUR_MFMA", "f3") : GRAM_F32_DEFAULT;
   bool fuse_update = !is("DBA_BA_FUSE_UPDATE", "0");   // see ba_run_loop
+  // stage 0 of a keyed call: a workgroup of its first linearisation ("fold") or a launch of its own in front of it ("launch")
+  bool stage0_fold = getenv("DBA_BA_STAGE0") ? is("DBA_BA_STAGE0", "fold") : STAGE0_FOLD_DEFAULT;
 };
 static const BaEnv &ba_env() { static const BaEnv env; return env; }
 
@@ -241,20 +244,26 @@ static int ba_prepare_stage(const BaPlan &plan, const int64_t *ii, const int64_t
 
 // upd: 0 = linearise the state as stored; bit 0 = poses still need Exp(W.dx) (retracted on the fly, the retracted window is
 // stored in poses_out), bit 1 = the depths still need the previous iteration's dz (applied in place in disps_w)
+// s0 (may be null; ba_stage0_folds() holds and upd = 0): the launch carries stage 0 as one more workgroup and reads no table
 static int ba_linearize_stage(const BaPlan &plan, const BaProblem &g, const float *poses, const float *disps, float alpha,
-                              int upd, float *poses_out, float *disps_w, hipStream_t stream) {
+                              int upd, float *poses_out, float *disps_w, hipStream_t stream, const BaStage0 *s0 = nullptr) {
   if (!poses || !disps || !g.intrinsics || !g.disps_sens || !g.eta || g.eta_rows < 1) return DBA_ERR_ARG;
   // eta has one row per entry of kx, or one row that is broadcast (eta.view(-1, HW), droid_kernels.cu:1476); more rows
   // than kx can have entries cannot be right (the exact |kx| is only known on the device: see droid_backends._ba_args)
   if (g.eta_rows > 1 && g.eta_rows > plan.T.Mmax) return DBA_ERR_ARG;
   if (plan.N > 0 && (!g.targets || !g.weights || !g.jj)) return DBA_ERR_ARG;
   // (EW waves share a pixel slice and split the frame's edges: EW times as many workgroups of four waves)
-#define LAUNCH_LIN(PPL, MF, EW)                                                                                          \
-  hipLaunchKernelGGL((ba_linearize_kernel<PPL, MF, EW>), dim3(plan.nchunks * EW, plan.T.Mmax + 1), dim3(256), 0, stream, \
-                     poses, disps, g.intrinsics, g.disps_sens, g.targets, g.weights, g.eta, g.eta_rows, g.jj,            \
-                     g.frame_owned, plan.N, plan.HW, plan.wd, plan.t0, plan.P, alpha, upd, poses_out, disps_w, plan.T, plan.W)
-  if (plan.W.ppl == 4) LAUNCH_LIN(4, false, 1);
-  else if (plan.W.ppl == 2) LAUNCH_LIN(2, false, 1);
+  if (s0 && (upd != 0 || plan.W.ppl != 1)) return DBA_ERR_ARG;
+  const BaStage0 none = {nullptr, 0, 0, nullptr, nullptr, 0};
+  // (folded: one more row of workgroups, whose first one is stage 0)
+#define LAUNCH_LIN_TF(PPL, MF, EW, TF)                                                                                        \
+  hipLaunchKernelGGL((ba_linearize_kernel<PPL, MF, EW, TF>), dim3(plan.nchunks * EW, plan.T.Mmax + (TF ? 2 : 1)), dim3(256), 0, \
+                     stream, poses, disps, g.intrinsics, g.disps_sens, g.targets, g.weights, g.eta, g.eta_rows, g.jj,         \
+                     g.frame_owned, plan.N, plan.HW, plan.wd, plan.t0, plan.P, alpha, upd, poses_out, disps_w, plan.T, plan.W, \
+                     TF ? *s0 : none)
+#define LAUNCH_LIN(PPL, MF, EW) do { if (s0) LAUNCH_LIN_TF(PPL, MF, EW, true); else LAUNCH_LIN_TF(PPL, MF, EW, false); } while (0)
+  if (plan.W.ppl == 4) LAUNCH_LIN_TF(4, false, 1, false);
+  else if (plan.W.ppl == 2) LAUNCH_LIN_TF(2, false, 1, false);
   else if (ba_env().lin_no_mfma) LAUNCH_LIN(1, false, 1);
   else {
     // Two waves per pixel slice halve a wave's life but pay the prologue / epilogue (5.9 of ~19 us at 64 KF / 512 edges) twice:
@@ -267,6 +276,7 @@ static int ba_linearize_stage(const BaPlan &plan, const BaProblem &g, const floa
     else LAUNCH_LIN(1, true, 2);
   }
 #undef LAUNCH_LIN
+#undef LAUNCH_LIN_TF
   DBA_LAUNCH_CHECK();
   return DBA_OK;
 }
@@ -360,10 +370,25 @@ static int ba_update_launch(const BaPlan &plan, float *poses, float *disps, cons
   return DBA_OK;
 }
 
+// A keyed call (prepared = 2) whose stage 0 rides in its first linearisation (ba_linearize_kernel<.., TF = true>) instead of
+// being a launch in front of it: a single-GPU call (no ownership mask, no exchange, its own skyline) with at least one iteration,
+// one pixel per lane and a window within the fold's bounds (ba_kernels.h).  DBA_BA_STAGE0=launch keeps the separate launch.
+static bool ba_stage0_folds(const BaPlan &plan, const BaProblem &g, const BaRun &run) {
+  return ba_env().stage0_fold && run.prepared == 2 && run.iterations > 0 && !g.frame_owned && !run.exchange && !run.window_fpose &&
+         plan.W.ppl == 1 && plan.N <= FOLD_MAX_N && plan.B <= FOLD_MAX_B && (plan.N == 0 || (g.ii && g.jj));
+}
+
 int ba_run_loop(const BaPlan &plan, const BaProblem &g, float *poses, float *disps, const BaRun &run, hipStream_t stream) {
   const int *fpose = run.window_fpose ? run.window_fpose : plan.T.fpose;
   int rc;
-  if (run.prepared != 1) {
+  const bool fold = ba_stage0_folds(plan, g, run);
+  BaStage0 s0 = {nullptr, 0, 0, nullptr, nullptr, 0};
+  if (fold) {   // ba_prepare_stage's arguments
+    const int max_nt = ba_solve_wave_max_nt(6 * plan.P);
+    s0.ii = g.ii, s0.t1 = plan.t1, s0.ftable = ba_schur_frame_form(plan.N, plan.P) ? 1 : 0;
+    s0.status = g.eta_rows > 1 ? ws_eta_status(plan.T.meta) : nullptr;
+    s0.band_verdict = max_nt ? solver_verdict_slot(plan.T.meta) : nullptr, s0.max_nt = max_nt;
+  } else if (run.prepared != 1) {
     rc = ba_prepare_stage(plan, g.ii, g.jj, g.eta_rows, run.prepared == 2, run.window_fpose == nullptr, stream);
     if (rc != DBA_OK) return rc;
   }
@@ -377,7 +402,8 @@ int ba_run_loop(const BaPlan &plan, const BaProblem &g, float *poses, float *dis
   for (int itr = 0; itr < run.iterations; itr++) {
     float *pose_dst = plan.W.poses_tmp + (size_t)(itr & 1) * 7 * plan.B;
     const int upd = pending ? (run.motion_only ? 1 : 3) : 0;
-    rc = ba_linearize_stage(plan, g, pose_src, disps, run.alpha, upd, pending ? pose_dst : nullptr, disps, stream);
+    rc = ba_linearize_stage(plan, g, pose_src, disps, run.alpha, upd, pending ? pose_dst : nullptr, disps, stream,
+                            (fold && itr == 0) ? &s0 : nullptr);
     if (rc != DBA_OK) return rc;
     if (pending) pose_src = pose_dst;
     rc = ba_reduce_stage(plan, g.ii, g.jj, g.frame_owned, run.motion_only, 1, stream);

@@ -80,12 +80,27 @@ __global__ void ba_prepare_kernel(const int64_t *ii, const int64_t *jj, int N, i
                                   int ftable, int check, int eta_rows, int *status, BaTables T, int *band_verdict, int max_nt);
 // which Schur kernel a window gets (ba_host.hip): the per-source-frame form on windows whose frames couple many rows
 bool ba_schur_frame_form(int N, int P);
-template <int PPL, bool MF, int EW>
+// Stage 0 folded into the first linearisation of a keyed call (ba_linearize_kernel<.., TF = true>, ba_run_loop): what that
+// launch needs besides the linearisation's own arguments -- the source frames, and ba_prepare_kernel's arguments for the one
+// workgroup that runs its body (check = 1; 256 threads, its LDS is the linearisation's staging tiles).
+struct BaStage0 {
+  const int64_t *ii;
+  int t1, ftable;
+  int *status, *band_verdict;
+  int max_nt;
+};
+// The windows the fold takes.  N: a lane of the linearisation's 256 per edge (one load of ii and of jj per lane), which is also
+// what the 256-thread stage 0 builds the frame row table for (its one-pass form needs an edge per thread).  B: the frames of
+// arange(t0, t1) U ii are a bit set of B / 32 words in LDS that every lane sums once.  Larger windows keep the separate launch.
+constexpr int FOLD_MAX_N = 256, FOLD_MAX_B = 512;
+constexpr int FOLD_SCAN_INTS = FOLD_MAX_B + 32;   // scan_ints of the folded stage 0: max(256 threads, P <= B) + 32
+template <int PPL, bool MF, int EW, bool TF>
 __global__ void ba_linearize_kernel(const float *poses, const float *disps, const float *intrinsics,
                                     const float *disps_sens, const float *targets, const float *weights,
                                     const float *eta, int eta_rows, const int64_t *jj,
                                     const uint8_t *frame_owned, int N, int HW, int wd, int t0, int P,
-                                    float alpha, int upd, float *poses_out, float *disps_w, BaTables T, BaBuffers W);
+                                    float alpha, int upd, float *poses_out, float *disps_w, BaTables T, BaBuffers W,
+                                    BaStage0 S0);
 // lower (here and below): bit 0 = only the lower triangle of H is kept up (what the solvers read), bit 1 = deterministic
 // accumulation (64-bit fixed point, see acc_add in ba_kernels.hip)
 __global__ void ba_assemble_kernel(const int64_t *ii, const int64_t *jj, const uint8_t *frame_owned, int N,

@@ -44,13 +44,12 @@ __device__ __forceinline__ int wave_incl_scan(int v, int lane) {
 }
 
 // One workgroup (a multiple of 64 threads, sized by the host to the graph: barriers among 2 waves are several times
-// cheaper than among 16).  LDS: flag[B] cnt[Mmax + 1] kxs[Mmax] scan[max(blockDim, 1024 if N > blockDim)].
-__global__ __launch_bounds__(1024) void ba_prepare_kernel(const int64_t *__restrict__ ii,
-                                                          const int64_t *__restrict__ jj, int N, int B,
-                                                          int t0, int t1, int scan_ints, int ftable, int check,
-                                                          int eta_rows, int *__restrict__ status, BaTables T,
-                                                          int *__restrict__ band_verdict, int max_nt) {
-  extern __shared__ int sm[];
+// cheaper than among 16).  LDS (sm): flag[B] cnt[Mmax + 1] kxs[Mmax] scan[max(blockDim, 1024 if N > blockDim)] vcnt[Mmax + 1].
+// The body of stage 0, shared by its own kernel and by the workgroup that the first linearisation of a keyed call carries
+// (ba_linearize_kernel<.., TF = true>): every thread of the workgroup calls it.
+__device__ void ba_prepare_body(int *sm, const int64_t *__restrict__ ii, const int64_t *__restrict__ jj, int N, int B, int t0,
+                                int t1, int scan_ints, int ftable, int check, int eta_rows, int *__restrict__ status,
+                                const BaTables &T, int *__restrict__ band_verdict, int max_nt) {
   int *flag = sm;
   int *cnt = sm + B;
   int *kxs = cnt + T.Mmax + 1;
@@ -312,6 +311,15 @@ __global__ __launch_bounds__(1024) void ba_prepare_kernel(const int64_t *__restr
     int *key = T.gkey;
     key[0] = GKEY_MAGIC, key[1] = N, key[2] = B, key[3] = t0, key[4] = t1, key[5] = ftable, key[6] = T.Mmax;   // (key[7]: check_eta)
   }
+}
+
+__global__ __launch_bounds__(1024) void ba_prepare_kernel(const int64_t *__restrict__ ii,
+                                                          const int64_t *__restrict__ jj, int N, int B,
+                                                          int t0, int t1, int scan_ints, int ftable, int check,
+                                                          int eta_rows, int *__restrict__ status, BaTables T,
+                                                          int *__restrict__ band_verdict, int max_nt) {
+  extern __shared__ int sm[];
+  ba_prepare_body(sm, ii, jj, N, B, t0, t1, scan_ints, ftable, check, eta_rows, status, T, band_verdict, max_nt);
 }
 
 // expSE3 / retrSE3 (droid_kernels.cu:113-178, :922-940); quaternion deliberately not renormalised.
@@ -603,16 +611,28 @@ __device__ unsigned long long g_lin_span[2 * 8192];
 // (C, w, Ei, Hii, vi) meet in LDS at the end.
 // (one pixel per lane: four workgroups per CU, i.e. every workgroup of a 25-keyframe window resident at once, is worth
 // keeping: the register budget is held at 128)
-template <int PPL, bool MF, int EW>
+//
+// TF ("table-free"): the first linearisation of a keyed call (dba_ba_run with prepared = 2: ba_run_loop).  Stage 0 is not a launch
+// of its own in front of it but ONE MORE WORKGROUP of this launch (an appended grid row, so no other block index moves): it
+// compares the call's edge list with the workspace's key and rebuilds the tables when they differ, exactly as ba_prepare_kernel
+// does.  The other workgroups therefore must not read a table: each derives what it needs of them -- |kx|, its slot's frame, its
+// slot's out-edges in ascending edge id -- from ii, jj, t0, t1, B in its prologue (one round trip to memory: a lane per edge,
+// the frames of arange(t0, t1) U ii as a B-bit set in LDS, ballots for the edge list).  Everything indexed by edge id (rows of
+// E, HpartE, Aedge) and every sum is what the table-driven kernel computes, bit for bit.  Needs N <= FOLD_MAX_N (a lane per
+// edge; also what the 256 threads of the stage-0 workgroup take in one pass) and B <= FOLD_MAX_B (the set's words); upd = 0.
+template <int PPL, bool MF, int EW, bool TF>
 __global__ __launch_bounds__(256, (PPL == 1 ? (MF ? 4 : 2) : 1)) void ba_linearize_kernel(
     const float *__restrict__ poses, const float *__restrict__ disps, const float *__restrict__ intrinsics,
     const float *__restrict__ disps_sens, const float *__restrict__ targets,
     const float *__restrict__ weights, const float *__restrict__ eta, int eta_rows,
     const int64_t *__restrict__ jj, const uint8_t *__restrict__ frame_owned, int N, int HW, int wd,
     int t0, int P, float alpha, int upd_arg, float *__restrict__ poses_out, float *__restrict__ disps_w, BaTables T,
-    BaBuffers W) {
+    BaBuffers W, BaStage0 S0) {
   // (a call whose eta does not fit its graph changes nothing: stage 0 left its verdict in the workspace, see check_eta)
-  const int upd = T.gkey[7] ? 0 : upd_arg;
+  // (TF: nothing is pending in front of a call's first linearisation, and a pending update is all that verdict switches off in
+  // this kernel -- eta_rows > 1 && eta_rows != |kx| has nothing to stop here; the stage-0 workgroup of this launch leaves it in
+  // gkey[7] for the launches behind it)
+  const int upd = TF ? 0 : (T.gkey[7] ? 0 : upd_arg);
   // upd != 0: the back-substitution + retraction of the PREVIOUS Gauss-Newton iteration is folded into this launch
   // (dba_ba: one launch and one kernel boundary less per iteration).  W.dx, W.E, W.Q, W.w still hold that iteration's
   // values: a workgroup first moves the depths of its own pixels (bit 1; nobody else reads them: the linearisation only
@@ -622,7 +642,27 @@ __global__ __launch_bounds__(256, (PPL == 1 ? (MF ? 4 : 2) : 1)) void ba_lineari
   unsigned long long lp_ = wall_clock64();
   const unsigned long long lp_start_ = lp_;
 #endif
+  // The out-edges of the frame are resolved in batches of up to EB by the first wave, one edge per lane
+  // (elist -> jj -> poses is a chain of three dependent global loads: paid once per batch, not per edge);
+  // the per-edge relative pose then comes out of LDS, and the next edge's targets/weights are in flight
+  // while the current edge is being reduced.
+  constexpr int EB = 16;            // (16, not 64: with the staging tiles below the workgroup then needs 40 KB of LDS and
+                                    // four of them fit a CU: every workgroup of a 25-keyframe window is resident at once)
+  __shared__ float s_pose[EB][12];  // tij[3], R[9]
+  __shared__ __attribute__((aligned(16))) float s_adj[EB][28];  // the 27 non-zero entries of A (Ji = Jj A): [k < 3][6] then [3 + k][3]
+  __shared__ int s_edge[EB][2];     // edge id, target frame
+  constexpr int RED_FLOATS = MF ? MFS_FLOATS : 64 * RED_PITCH;
+  __shared__ __attribute__((aligned(16))) float s_red[4][RED_FLOATS];  // per-wave transpose tiles / MFMA staging
   const int m = blockIdx.y;
+  if constexpr (TF) {
+    if (m == T.Mmax + 1) {  // the appended row: its first workgroup is stage 0 (the staging tiles are its LDS)
+      static_assert(!TF || 4 * FOLD_MAX_B + 2 + FOLD_SCAN_INTS <= 4 * RED_FLOATS, "stage 0 does not fit the staging tiles");
+      if (blockIdx.x == 0)
+        ba_prepare_body(reinterpret_cast<int *>(&s_red[0][0]), S0.ii, jj, N, T.B, t0, S0.t1, FOLD_SCAN_INTS, S0.ftable, 1, eta_rows,
+                        S0.status, T, S0.band_verdict, S0.max_nt);
+      return;
+    }
+  }
   if (m == T.Mmax) {  // extra row of workgroups: clear the reduced camera system for stage 2
     const int n6 = 6 * P;
     const size_t total = (size_t)n6 * n6;
@@ -640,10 +680,56 @@ __global__ __launch_bounds__(256, (PPL == 1 ? (MF ? 4 : 2) : 1)) void ba_lineari
     }
     return;
   }
-  const int M = T.meta[0];
-  if (m >= M) return;
-  const int frame = T.kx[m];
-  if (frame_owned && !frame_owned[frame]) return;
+  int frame, e0 = 0, e1 = 0;
+  __shared__ int2 s_out[TF ? FOLD_MAX_N : 1];   // TF: the slot's out-edges (edge id, target frame), ascending edge id: T.einfo's rows
+  if constexpr (TF) {
+    __shared__ unsigned s_fmask[FOLD_MAX_B / 32];   // which frames have a slot: arange(t0, t1) U ii
+    __shared__ int s_wcnt[4];
+    const int tid = threadIdx.x;
+    const int my_i = (tid < N) ? (int)S0.ii[tid] : -1, my_j = (tid < N) ? (int)jj[tid] : -1;
+    if (tid < FOLD_MAX_B / 32) {   // the window's own frames (0 <= t0 <= t1 <= B: ba_plan)
+      const int lo = min(max(t0 - 32 * tid, 0), 32), hi = min(max(S0.t1 - 32 * tid, 0), 32);
+      const unsigned below_hi = (hi >= 32) ? ~0u : ((1u << hi) - 1u), below_lo = (lo >= 32) ? ~0u : ((1u << lo) - 1u);
+      s_fmask[tid] = below_hi & ~below_lo;
+    }
+    __syncthreads();
+    if (my_i >= 0 && my_i < T.B) atomicOr(&s_fmask[my_i >> 5], 1u << (my_i & 31));
+    __syncthreads();
+    // slot m is the set's m-th member (kx is the sorted set); |kx| its size
+    int M = 0, word = 0, skip = 0;
+    unsigned bits = 0;
+    bool found = false;
+#pragma unroll
+    for (int w = 0; w < FOLD_MAX_B / 32; w++) {
+      const unsigned b = s_fmask[w];
+      const int c = __popc(b);
+      if (!found && m < M + c) found = true, word = w, bits = b, skip = m - M;
+      M += c;
+    }
+    if (m >= min(M, T.Mmax)) return;
+    for (int r = 0; r < skip; r++) bits &= bits - 1;
+    frame = 32 * word + __ffs(bits) - 1;
+    if (frame_owned && !frame_owned[frame]) return;
+    // its out-edges: the lanes whose edge leaves this frame, in lane (= edge id) order
+    const bool mine = my_i == frame;
+    const unsigned long long bal = __ballot(mine);
+    if ((tid & 63) == 0) s_wcnt[tid >> 6] = __popcll(bal);
+    __syncthreads();
+    int before = 0;
+#pragma unroll
+    for (int w = 0; w < 4; w++) {
+      const int c = s_wcnt[w];
+      before += (w < (tid >> 6)) ? c : 0;
+      e1 += c;
+    }
+    if (mine) s_out[before + __popcll(bal & ((1ull << (tid & 63)) - 1ull))] = make_int2(tid, my_j);
+    // (the walk's first barrier orders the list before its readers)
+  } else {
+    const int M = T.meta[0];
+    if (m >= M) return;
+    frame = T.kx[m];
+    if (frame_owned && !frame_owned[frame]) return;
+  }
 
   const int lane = lane_id();
   const int wv = threadIdx.x >> 6, ew = wv % EW;  // ew: which share of the edges this wave takes
@@ -685,27 +771,16 @@ __global__ __launch_bounds__(256, (PPL == 1 ? (MF ? 4 : 2) : 1)) void ba_lineari
 #pragma unroll
     for (int c = 0; c < 6; c++) Ei[q][c] = 0.f;
   }
-  // The out-edges of the frame are resolved in batches of up to EB by the first wave, one edge per lane
-  // (elist -> jj -> poses is a chain of three dependent global loads: paid once per batch, not per edge);
-  // the per-edge relative pose then comes out of LDS, and the next edge's targets/weights are in flight
-  // while the current edge is being reduced.
-  constexpr int EB = 16;            // (16, not 64: with the staging tiles below the workgroup then needs 40 KB of LDS and
-                                    // four of them fit a CU: every workgroup of a 25-keyframe window is resident at once)
-  __shared__ float s_pose[EB][12];  // tij[3], R[9]
-  __shared__ __attribute__((aligned(16))) float s_adj[EB][28];  // the 27 non-zero entries of A (Ji = Jj A): [k < 3][6] then [3 + k][3]
-  __shared__ int s_edge[EB][2];     // edge id, target frame
-  constexpr int RED_FLOATS = MF ? MFS_FLOATS : 64 * RED_PITCH;
-  __shared__ __attribute__((aligned(16))) float s_red[4][RED_FLOATS];  // per-wave transpose tiles / MFMA staging
   float *red_wave = s_red[wv];
   float *red_lane = red_wave + lane;
-  const int e0 = T.eoff[m], e1 = T.eoff[m + 1];
+  if constexpr (!TF) e0 = T.eoff[m], e1 = T.eoff[m + 1];
   LP(0);
   for (int batch = e0; batch < e1; batch += EB) {
     const int cnt = min(EB, e1 - batch);
     __syncthreads();
     LP(1);
     if ((int)threadIdx.x < cnt) {
-      const int2 ei = *reinterpret_cast<const int2 *>(T.einfo + 2 * (batch + threadIdx.x));
+      const int2 ei = TF ? s_out[batch + threadIdx.x] : *reinterpret_cast<const int2 *>(T.einfo + 2 * (batch + threadIdx.x));
       const int n = ei.x, jx = ei.y;
       // The relative pose Tj Ti^-1 of the edge is formed in FLOAT64 from the float poses and rounded once: its translation
       // tj - Rij ti is a difference of two absolute positions, which in float costs ~20 x the rounding of the result -- on
@@ -973,26 +1048,20 @@ extern "C" void dba_lin_prof_dump() {
 }
 #endif
 
-template __global__ void ba_linearize_kernel<1, true, 2>(const float *, const float *, const float *, const float *,
-                                                const float *, const float *, const float *, int, const int64_t *,
-                                                const uint8_t *, int, int, int, int, int, float, int, float *, float *,
-                                                BaTables, BaBuffers);
-template __global__ void ba_linearize_kernel<1, true, 1>(const float *, const float *, const float *, const float *,
-                                                const float *, const float *, const float *, int, const int64_t *,
-                                                const uint8_t *, int, int, int, int, int, float, int, float *, float *,
-                                                BaTables, BaBuffers);
-template __global__ void ba_linearize_kernel<1, false, 1>(const float *, const float *, const float *, const float *,
-                                                const float *, const float *, const float *, int, const int64_t *,
-                                                const uint8_t *, int, int, int, int, int, float, int, float *, float *,
-                                                BaTables, BaBuffers);
-template __global__ void ba_linearize_kernel<2, false, 1>(const float *, const float *, const float *, const float *,
-                                                const float *, const float *, const float *, int, const int64_t *,
-                                                const uint8_t *, int, int, int, int, int, float, int, float *, float *,
-                                                BaTables, BaBuffers);
-template __global__ void ba_linearize_kernel<4, false, 1>(const float *, const float *, const float *, const float *,
-                                                const float *, const float *, const float *, int, const int64_t *,
-                                                const uint8_t *, int, int, int, int, int, float, int, float *, float *,
-                                                BaTables, BaBuffers);
+#define LIN_INST(PPL, MF, EW, TF)                                                                                          \
+  template __global__ void ba_linearize_kernel<PPL, MF, EW, TF>(const float *, const float *, const float *, const float *,  \
+                                                                const float *, const float *, const float *, int,            \
+                                                                const int64_t *, const uint8_t *, int, int, int, int, int,   \
+                                                                float, int, float *, float *, BaTables, BaBuffers, BaStage0)
+LIN_INST(1, true, 2, false);
+LIN_INST(1, true, 1, false);
+LIN_INST(1, false, 1, false);
+LIN_INST(2, false, 1, false);
+LIN_INST(4, false, 1, false);
+LIN_INST(1, true, 2, true);   // (one pixel per lane only: the windows that get more are launches of hundreds of microseconds)
+LIN_INST(1, true, 1, true);
+LIN_INST(1, false, 1, true);
+#undef LIN_INST
 
 // ---------------------------------------------------------------------------------------------
 // stage 2: reduced camera system in float64
