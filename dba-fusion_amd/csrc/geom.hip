@@ -12,6 +12,7 @@
 
 #include "common.h"
 #include "frame_distance.h"
+#include "geom_pixel.h"
 #include "reproj.h"
 
 namespace dba {
@@ -81,17 +82,12 @@ __global__ __launch_bounds__(256) void iproj_kernel(const float *__restrict__ po
   const int b = blockIdx.y;
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= HW) return;
-  const float *t = poses + 7 * b;
-  const Rot3 R = quat_to_rot(poses + 7 * b + 3);
-  const float fx = intr[0], fy = intr[1], cx = intr[2], cy = intr[3];
-  const float u = (float)(k % wd), v = (float)(k / wd);
-  const float d = disps[(size_t)b * HW + k];
   float x, y, z;
-  act_point(R, t, (u - cx) / fx, (v - cy) / fy, d, x, y, z);
+  iproj_pixel(poses, disps, intr, b, k, HW, wd, x, y, z);
   float *p = points + ((size_t)b * HW + k) * 3;
-  p[0] = x / d;
-  p[1] = y / d;
-  p[2] = z / d;
+  p[0] = x;
+  p[1] = y;
+  p[2] = z;
 }
 
 __global__ __launch_bounds__(256) void depth_filter_kernel(const float *__restrict__ poses,
@@ -100,39 +96,12 @@ __global__ __launch_bounds__(256) void depth_filter_kernel(const float *__restri
                                                            const int64_t *__restrict__ inds,
                                                            const float *__restrict__ thresh, int nbuf, int ht,
                                                            int wd, float *__restrict__ counter) {
-  // one lane per (keyframe, pixel); the six neighbours are visited in order so no atomics are needed
+  // one lane per (keyframe, pixel)
   const int b = blockIdx.y;
   const int HW = ht * wd;
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= HW) return;
-  const int ix = (int)inds[b];
-  const float fx = intr[0], fy = intr[1], cx = intr[2], cy = intr[3];
-  const float t = thresh[b];
-  const float u = (float)(k % wd), v = (float)(k / wd);
-  const float X0 = (u - cx) / fx, X1 = (v - cy) / fy;
-  const float di = disps[(size_t)ix * HW + k];
-  float count = 0.f;
-  for (int neigh = 0; neigh < 6; neigh++) {
-    const int jx = (neigh < 3) ? ix - neigh - 1 : ix + neigh;  // :740
-    if (jx < 0 || jx >= nbuf) continue;
-    float tij[3], qij[4];
-    rel_pose(poses + 7 * ix, poses + 7 * jx, tij, qij);
-    const Rot3 R = quat_to_rot(qij);
-    float x, y, z;
-    act_point(R, tij, X0, X1, di, x, y, z);
-    const float uj = fx * (x / z) + cx, vj = fy * (y / z) + cy;
-    const float dj = di / z;
-    const int u0 = (int)floorf(uj), v0 = (int)floorf(vj);
-    if (u0 >= 0 && v0 >= 0 && u0 < wd - 1 && v0 < ht - 1) {
-      const float *dp = disps + (size_t)jx * HW + (size_t)v0 * wd + u0;
-      const double idj = 1.0 / (double)dj;  // abs(1.0/dj - 1.0/d00) is double arithmetic (:813-817)
-      const double tt = (double)t;
-      if (fabs(idj - 1.0 / (double)dp[0]) < tt) count += 1.f;
-      else if (fabs(idj - 1.0 / (double)dp[1]) < tt) count += 1.f;
-      else if (fabs(idj - 1.0 / (double)dp[wd]) < tt) count += 1.f;
-      else if (fabs(idj - 1.0 / (double)dp[wd + 1]) < tt) count += 1.f;
-    }
-  }
+  const float count = depth_filter_pixel(poses, disps, intr, (int)inds[b], thresh[b], nbuf, ht, wd, k);
   counter[(size_t)b * HW + k] += count;
 }
 

@@ -189,6 +189,9 @@ SYMBOLS = {
     "dba_enc_context_split": (c_int, [_P] + [c_int] * 5 + [_P, _P, _P]),
     "dba_upd_heads": (c_int, [ctypes.POINTER(UpdHead)] + [c_int] * 6 + [_P]),
     "dba_upd_heads_tile": (c_int, [ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "dba_archive_frames": (c_int, [_P] * 10 + [c_int] * 9 + [ctypes.c_int64, _P]),
+    "dba_map_plan": (c_int, [_P] * 3 + [c_int] * 5 + [_P] * 9 + [ctypes.POINTER(c_int), _P]),
+    "dba_map_payload": (c_int, [_P] * 6 + [c_int] * 4 + [ctypes.c_int64, _P, _P, _P]),
 }
 
 _lib = None

@@ -1011,6 +1011,39 @@ typedef struct {
 int dba_upd_heads(const dba_upd_head_t *heads, int n_heads, int n, int c, int ht, int wd, int dtype, dba_stream_t stream);
 int dba_upd_heads_tile(int *rows, int *cols); /* the kernel's tile extents, for the tests */
 
+/* ---- map export (csrc/map_export.hip) ---------------------------------------------------------------------------------
+ * The keyframe archive of DepthVideo.ba (dbaf/depth_video.py:337-343, :379-385) and the point cloud of save_vis_easy
+ * (dbaf/dbaf.py:64-140).  All pointers are device pointers unless named otherwise; nothing is read back by the library.
+ *
+ * dba_archive_frames: ONE launch.  Frames [i0, i1) of the video buffers go to rows [row, row + i1 - i0) of the save buffers:
+ *   tstamp (double), disps [.., ht, wd], poses [.., 7] and, when disps_up / disps_up_save are not null, disps_up (rows of
+ *   up_elems floats) are row copies; images_save[r, y, x, c] = float(images[i, 2 - c, 8 y, 8 x]) * (1.0f / 255.0f), the bits
+ *   torch writes for `images[i, [2,1,0], ::8, ::8].permute(1,2,0) / 255.0` on device tensors (it multiplies by the float32
+ *   reciprocal of a host scalar).  images is uint8 [n_src, 3, img_h, img_w]; needs ht == ceil(img_h / 8), wd == ceil(img_w / 8),
+ *   0 <= i0, i1 <= n_src, 0 <= row, row + (i1 - i0) <= n_dst, i1 - i0 <= 65535.  i1 <= i0: no launch.
+ * dba_map_plan: per archived frame b < count: means[b] (float32 mean of disps_save[b]: lane l of 256 adds pixels l, l + 256,
+ *   ...; a wave tree; the four wave totals in wave order; one IEEE division), inv_poses[b] (SE3(pose).inv(), 7 floats) and
+ *   cameras[b] (its 4x4 matrix, row-major).  scalars[0] = the lower median of the means (torch.median), scalars[1] = the
+ *   threshold: ((0.4f * 1.0f) / 4.0f) * (1.0f / median) when min_count > 0 (filtered), 0.4f otherwise (raw, unused).
+ *   counts [count, ht, wd] (filtered only): the depth-filter count with neighbours over ALL `rows` rows of the save buffers;
+ *   mask [count, ht, wd] (bytes 0 / 1): (counts >= min_count) & (disp > 0.5f * means[b]), raw: the second clause alone, and no
+ *   depth-filter code runs; frame_counts [count] (int): survivors per frame; offsets [count + 1]: their exclusive scan,
+ *   offsets[count] the total.  tickets: two ints, ZERO on entry.  *launches (host): the launches enqueued, 2 filtered, 1 raw.
+ *   Needs 0 <= count <= rows, ht, wd >= 1; the save buffers have `rows` rows.  count == 0: no launch.
+ * dba_map_payload: ONE launch.  pts [total, 3] = the points of the surviving pixels (iproj on inv_poses), clr [total, 3] their
+ *   rows of images_save [rows, ht, wd, 3], frame-major and row-major within a frame; total == offsets[count] as the host
+ *   read it.  total == 0: no launch. */
+int dba_archive_frames(const double *tstamp, const float *disps, const float *poses, const float *disps_up,
+                       const uint8_t *images, double *tstamp_save, float *disps_save, float *poses_save,
+                       float *disps_up_save, float *images_save, int n_src, int n_dst, int i0, int i1, int row, int ht,
+                       int wd, int img_h, int img_w, int64_t up_elems, dba_stream_t stream);
+int dba_map_plan(const float *poses_save, const float *disps_save, const float *intrinsics, int count, int rows, int ht,
+                 int wd, int min_count, float *means, float *inv_poses, float *cameras, float *scalars, float *counts,
+                 uint8_t *mask, int *frame_counts, int64_t *offsets, int *tickets, int *launches, dba_stream_t stream);
+int dba_map_payload(const float *inv_poses, const float *disps_save, const float *intrinsics, const float *images_save,
+                    const uint8_t *mask, const int64_t *offsets, int count, int rows, int ht, int wd, int64_t total,
+                    float *pts, float *clr, dba_stream_t stream);
+
 #define DBA_PEER_TIMEOUT 1
 size_t dba_peer_exchange_bytes(size_t max_doubles);
 int dba_peer_exchange_create(size_t bytes, void **region, unsigned char *handle64);
