@@ -62,17 +62,11 @@ __global__ __launch_bounds__(512) void keyframe_check_kernel(const float *__rest
     }
     s_cam[threadIdx.x] = c;
   } else if (threadIdx.x == KF_MAX_WIN) {
-    // poses[t1-1].inv().matrix(): the columns of R are _qrot(qi, e_k), the fourth column is ti
-    float ti[3], qi[4];
-    kf_inv(poses + 7 * (t1 - 1), ti, qi);
+    // poses[t1-1].inv().matrix(), by the call that dba_world_poses (frames.hip) makes for every row: the same bits
+    const float *P = poses + 7 * (t1 - 1);
+    const KfMat34 M = kf_inv_matrix(P[0], P[1], P[2], P[3], P[4], P[5], P[6]);
 #pragma unroll
-    for (int k = 0; k < 3; k++) {
-      const float e[3] = {k == 0 ? 1.f : 0.f, k == 1 ? 1.f : 0.f, k == 2 ? 1.f : 0.f};
-      float col[3];
-      kf_qrot(qi, e, col);
-      s_mat[0 + k] = col[0]; s_mat[4 + k] = col[1]; s_mat[8 + k] = col[2];
-    }
-    s_mat[3] = ti[0]; s_mat[7] = ti[1]; s_mat[11] = ti[2];
+    for (int k = 0; k < 12; k++) s_mat[k] = M.m[k];
     s_mat[12] = 0.f; s_mat[13] = 0.f; s_mat[14] = 0.f; s_mat[15] = 1.f;
   }
   __syncthreads();

@@ -1,6 +1,6 @@
 // The lietorch shim's SE3.inv on a (t, q_xyzw) row (lietorch/__init__.py: _qinv, _qrot, SE3.inv), in its order of
-// operations, each spelled with an intrinsic the compiler does not fuse: the same bits in every translation unit.
-// Shared by keyframe_check_kernel (keyframe.hip) and the map export's plan launch (map_export.hip).
+// operations.  Shared by keyframe_check_kernel (keyframe.hip), the map export's plan launch (map_export.hip) and
+// world_poses_kernel (frames.hip).  Callers that need the same BITS for the same pose call kf_inv_matrix below.
 #pragma once
 #include "common.h"
 
@@ -30,6 +30,31 @@ __device__ __forceinline__ void kf_inv(const float *P, float *ti, float *qi) {
   float r[3];
   kf_qrot(qi, P, r);
   ti[0] = -r[0]; ti[1] = -r[1]; ti[2] = -r[2];
+}
+
+// poses[r].inv().matrix(), its first three rows (row-major 3 x 4): the columns of R are _qrot(qi, e_k), the fourth column is
+// ti.  NOT inlined.  To hipcc the intrinsics above are plain operators, and its backend fuses a product into a sum where it
+// finds one; which ones it finds depends on the code around an inlined copy (keyframe_check_kernel and a second kernel with
+// the same statements inlined differed in the last bits of ti).  A call is compiled once per translation unit from this text
+// alone, so keyframe_check_kernel (keyframe.hip) and world_poses_kernel (frames.hip), built with the same flags, give the
+// same bits for the same pose.
+struct KfMat34 {
+  float m[12];
+};
+static __device__ __noinline__ KfMat34 kf_inv_matrix(float tx, float ty, float tz, float qx, float qy, float qz, float qw) {
+  const float P[7] = {tx, ty, tz, qx, qy, qz, qw};
+  float ti[3], qi[4];
+  kf_inv(P, ti, qi);
+  KfMat34 M;
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    const float e[3] = {k == 0 ? 1.f : 0.f, k == 1 ? 1.f : 0.f, k == 2 ? 1.f : 0.f};
+    float col[3];
+    kf_qrot(qi, e, col);
+    M.m[0 + k] = col[0]; M.m[4 + k] = col[1]; M.m[8 + k] = col[2];
+  }
+  M.m[3] = ti[0]; M.m[7] = ti[1]; M.m[11] = ti[2];
+  return M;
 }
 
 }  // namespace dba

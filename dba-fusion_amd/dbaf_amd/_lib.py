@@ -55,6 +55,18 @@ class UpdHead(ctypes.Structure):
                 ("k", c_int), ("relu_in", c_int), ("act", c_int), ("scale", c_float)]
 
 
+class FrameItem(ctypes.Structure):
+    """dba_frame_item of include/dba_hip.h"""
+    _fields_ = [(n, c_void_p) for n in ("tstamp", "images", "poses", "disps", "disps_sens", "intrinsics", "fmaps", "nets",
+                                        "inps")] + \
+               [(n, c_int) for n in ("rows", "row", "ht", "wd")] + \
+               [(n, ctypes.c_int64) for n in ("fmap_row_bytes", "net_row_bytes", "inp_row_bytes")] + \
+               [("tstamp_value", ctypes.c_double)] + \
+               [(n, c_void_p) for n in ("image", "fmap", "net", "inp", "pose_dev", "intr_dev", "disp_dev", "depth")] + \
+               [(n, c_int) for n in ("pose_mode", "intr_mode", "disp_mode", "seed_disps")] + \
+               [("pose", c_float * 7), ("intr", c_float * 4), ("disp_fill", c_float)]
+
+
 # every exported symbol of include/dba_hip.h with its (restype, argtypes); pointers are void*
 _P = c_void_p
 SYMBOLS = {
@@ -192,6 +204,11 @@ SYMBOLS = {
     "dba_archive_frames": (c_int, [_P] * 10 + [c_int] * 9 + [ctypes.c_int64, _P]),
     "dba_map_plan": (c_int, [_P] * 3 + [c_int] * 5 + [_P] * 9 + [ctypes.POINTER(c_int), _P]),
     "dba_map_payload": (c_int, [_P] * 6 + [c_int] * 4 + [ctypes.c_int64, _P, _P, _P]),
+    "dba_frame_append": (c_int, [ctypes.POINTER(FrameItem), _P]),
+    "dba_frame_seed_next": (c_int, [_P, _P, _P] + [c_int] * 6 + [_P, ctypes.c_int64, _P]),
+    "dba_world_poses": (c_int, [_P, c_int, c_int, _P, _P]),
+    "dba_set_world_poses": (c_int, [_P, _P, c_int, c_int, ctypes.c_int64, c_int, c_int, _P, c_float, ctypes.POINTER(c_int),
+                                    _P]),
 }
 
 _lib = None

@@ -1044,6 +1044,55 @@ int dba_map_payload(const float *inv_poses, const float *disps_save, const float
                     const uint8_t *mask, const int64_t *offsets, int count, int rows, int ht, int wd, int64_t total,
                     float *pts, float *clr, dba_stream_t stream);
 
+/* ---- frame admission (csrc/frames.hip) --------------------------------------------------------------------------------
+ * How a frame enters and leaves the window: DepthVideo.append (dbaf/depth_video.py:129-159, :183-185), the seeds for the
+ * next frame (dbaf/dbaf_frontend.py:372-375, :841-849) and the pose hand-over with the host estimator (:224-228, :424-432,
+ * :553-570, :607-608, :809-814).  Device pointers unless named host.
+ *
+ * dba_frame_append: ONE launch that writes row `row` of the video buffers from a dba_frame_item (read on the host).
+ *   tstamp[row] = tstamp_value.  image / fmap / net / inp (null: the row is left alone) are dense rows moved by the row
+ *   mover's job table (csrc/row_jobs.h), rows of 3 * 64 ht wd, fmap_row_bytes, net_row_bytes, inp_row_bytes bytes; they must
+ *   not overlap the rows they are written to.  pose (7 floats) and intr (4 floats): DBA_FR_SKIP, DBA_FR_HOST (the values of
+ *   the struct, carried in the kernel's arguments) or DBA_FR_DEVICE (pose_dev / intr_dev are read by the launch).  disp:
+ *   DBA_FR_SKIP, DBA_FR_HOST (every entry of disps[row] = disp_fill) or DBA_FR_DEVICE (disp_dev, [ht, wd]).  depth (null, or
+ *   [8 ht, 8 wd] floats): disps_sens[row][y, x] = d > 0 ? 1 / d : d with d = depth[8 y + 3, 8 x + 3], one IEEE division.
+ *   seed_disps != 0: afterwards disps[row] = disps_sens[row] > 0 ? disps_sens[row] : disps[row] (dbaf_frontend.py:247-248),
+ *   on the values this call leaves in both rows.  Needs 0 <= row < rows, ht, wd >= 1.
+ * dba_frame_seed_next: ONE launch of one workgroup.  poses[t1] = poses[t1 - 1]; every entry of disps[t1] = the float32 mean
+ *   of disps[t1 - mean_rows : t1] in one fixed order (csrc/frames.hip); dirty[lo : t1] = 1 with lo = min(ii) clamped to
+ *   [0, t1], lo = 0 when ii is null.  Needs 1 <= mean_rows <= t1 < rows, t1 <= dirty_rows, mean_rows * ht * wd <= 2^24,
+ *   n_ii >= 1 when ii is not null.
+ * dba_world_poses: out_host[r] (16 floats, row-major) = SE3(poses[r]).inv().matrix() for r < n, by the routine of
+ *   dba_keyframe_check.  ONE launch into pinned memory of the library's, one host wait on a completion word (no stream
+ *   synchronisation), then a host copy into out_host.  Needs 1 <= n <= rows, n <= DBA_FR_MAX_ROWS.
+ * dba_set_world_poses: wTc_host: n row-major 4x4 doubles, camera-to-world, for rows [i0, i0 + n).  ONE launch: in float64,
+ *   world-to-camera as (R^T, -R^T t), the quaternion by the four-branch rule (the largest of the diagonal entries and the
+ *   trace picks the branch, the first on a tie; no sign canonicalisation), normalised, rounded to float32 into poses[i].
+ *   inv_scale != 0: disps[i] *= inv_scale on the same rows.  The matrices are staged through pinned memory of the library's:
+ *   wTc_host is free on return.  Nothing synchronises the stream; a completion word guards the staging block's reuse, and
+ *   *waited (host, may be null) says whether this call had to wait for it.  Needs 0 <= i0, i0 + n <= rows, 1 <= n <=
+ *   DBA_FR_MAX_ROWS, disps_rows >= i0 + n when inv_scale != 0. */
+#define DBA_FR_SKIP 0
+#define DBA_FR_HOST 1
+#define DBA_FR_DEVICE 2
+#define DBA_FR_MAX_ROWS 1024
+typedef struct dba_frame_item {
+  void *tstamp, *images, *poses, *disps, *disps_sens, *intrinsics, *fmaps, *nets, *inps; /* the video's buffers */
+  int rows, row, ht, wd;
+  int64_t fmap_row_bytes, net_row_bytes, inp_row_bytes;
+  double tstamp_value;
+  const void *image, *fmap, *net, *inp;
+  const float *pose_dev, *intr_dev, *disp_dev, *depth;
+  int pose_mode, intr_mode, disp_mode, seed_disps;
+  float pose[7], intr[4], disp_fill;
+} dba_frame_item;
+int dba_frame_append(const dba_frame_item *item_host, dba_stream_t stream);
+int dba_frame_seed_next(float *poses, float *disps, uint8_t *dirty, int rows, int dirty_rows, int ht, int wd, int t1,
+                        int mean_rows, const int64_t *ii, int64_t n_ii, dba_stream_t stream);
+int dba_world_poses(const float *poses, int rows, int n, float *out_host, dba_stream_t stream);
+int dba_set_world_poses(float *poses, float *disps, int rows, int disps_rows, int64_t map_elems, int i0, int n,
+                        const double *wTc_host, float inv_scale, int *waited, dba_stream_t stream);
+
 #define DBA_PEER_TIMEOUT 1
 size_t dba_peer_exchange_bytes(size_t max_doubles);
 int dba_peer_exchange_create(size_t bytes, void **region, unsigned char *handle64);
