@@ -16,6 +16,7 @@
 #include <stdint.h>
 
 #include "common.h"
+#include "cvx_weights.h"
 
 namespace dba {
 
@@ -77,16 +78,7 @@ __global__ __launch_bounds__(256) void cvx_upsample_kernel(const float *__restri
     const int y = p / wd, x = p - y * wd;
     py[v] = y;
     px[v] = x;
-#pragma unroll
-    for (int ky = 0; ky < 3; ++ky) {
-      const int yy = y + ky - 1;
-#pragma unroll
-      for (int kx = 0; kx < 3; ++kx) {
-        const int xx = x + kx - 1;
-        const bool in = yy >= 0 && yy < ht && xx >= 0 && xx < wd;
-        dk[v][ky * 3 + kx] = in ? d[yy * wd + xx] : 0.f;
-      }
-    }
+    cvx_taps(d, y, x, ht, wd, dk[v]);
   }
 
   const T *m = mask + ((size_t)f * 576 + (size_t)a * 8) * HW + p0;
@@ -98,24 +90,10 @@ __global__ __launch_bounds__(256) void cvx_upsample_kernel(const float *__restri
     for (int k = 0; k < 9; ++k) VecLoad<T, V>::run(m + (size_t)(k * 64 + b) * HW, e[k]);
 #pragma unroll
     for (int v = 0; v < V; ++v) {
-      float mx = e[0][v];
+      float ev[9];
 #pragma unroll
-      for (int k = 1; k < 9; ++k) mx = fmaxf(mx, e[k][v]);
-      float s = 0.f;
-#pragma unroll
-      for (int k = 0; k < 9; ++k) {
-        e[k][v] = __builtin_amdgcn_exp2f((e[k][v] - mx) * 1.4426950408889634f);
-        s += e[k][v];
-      }
-      const float inv = 1.f / s;
-      float r = 0.f;
-#pragma unroll
-      for (int k = 0; k < 9; ++k) {
-        float w = e[k][v] * inv;
-        if (sizeof(T) == 2) w = (float)(half_t)w;
-        r += w * dk[v][k];
-      }
-      res[v][b] = r;
+      for (int k = 0; k < 9; ++k) ev[k] = e[k][v];
+      res[v][b] = cvx_combine<sizeof(T) == 2>(ev, dk[v]);
     }
   }
 

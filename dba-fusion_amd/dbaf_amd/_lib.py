@@ -160,6 +160,10 @@ SYMBOLS = {
     "dba_peer_allreduce_f64": (c_int, [_P, c_size_t, _P, c_int, c_int, ctypes.c_uint, c_size_t, _P, _P]),
     "dba_cvx_upsample_disp": (c_int, [_P, c_int, _P, _P] + [c_int] * 4 + [_P, c_int, _P, _P]),
     "dba_segment_reduce": (c_int, [_P, c_int, _P, c_int, ctypes.c_int64, ctypes.c_int64, c_int, c_int, _P, _P]),
+    "dba_upmask_upsample_disp": (c_int, [_P] * 4 + [c_int, _P] + [c_int] * 3 + [_P, c_int, _P, _P, _P]),
+    "dba_frame_plan_max_rows": (c_int, []),
+    "dba_frame_plan": (c_int, [_P] + [c_int] * 3 + [_P, _P, _P, c_int, _P]),
+    "dba_frame_plan_poll": (c_int, [ctypes.POINTER(c_int)]),
     "dba_frame_distance_bidir": (c_int, [_P] * 5 + [c_int] * 4 + [c_float, _P, _P]),
     "dba_proximity_edges_capacity": (c_int, [c_int] * 5),
     "dba_proximity_edges": (c_int, [_P] * 3 + [c_int] * 7 + [c_float, ctypes.c_double, c_int, c_int, _P, c_int, c_int]

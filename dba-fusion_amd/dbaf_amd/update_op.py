@@ -21,8 +21,17 @@ Every fused piece routes on its own facts, as ConvGRU._fusable does: contiguous 
 float32}, the convolution answering in that dtype, nothing asking for a gradient; otherwise that piece runs the statements.
 One more fact for eta: torch's autocast runs softplus in float32, so under autocast the statements answer in float32 from
 a half convolution, and the piece runs them (the kernel rounds to the tensor dtype; it would lose those bits).  CPU tensors
-raise.  No host synchronisation on the upsample=False path (GraphAgg keeps torch.unique's host read), work is enqueued on
-torch.cuda.current_stream(), memory comes from torch's allocator only, and a forward can be captured into a hipGraph.
+raise.  No host synchronisation on the upsample=False path, work is enqueued on torch.cuda.current_stream(), memory comes
+from torch's allocator only, and a forward can be captured into a hipGraph.
+
+Upsample mode (upsample=True).  GraphAgg takes the frames of its edge list from frame_plan(ii, buffer) (csrc/upmask.hip,
+dba_frame_plan) in place of torch.unique, and sizes the segmented mean by it: the first forward on an edge list reads the
+plan's count once, every later forward on the same list reads nothing and can be captured.  `last_uniq` keeps the plan's
+frames for the caller's `self.damping[uniq] = damping` and `video.upsample(uniq, upmask)`.  With `fuse_upmask` set (default
+off: then nothing changes) and a half hidden state, the fifth return value is an UpmaskSource -- the operands of the mask's
+1x1 convolution, not its result -- which dbaf_amd.upsample.upsample_disps_ consumes in ONE launch (dba_upmask_upsample_disp);
+`.materialize()` gives the stock convolution's tensor to a caller that wants it.  Float32 modules, a gradient, a
+non-contiguous state keep the two launches.
 """
 import ctypes
 
@@ -31,6 +40,7 @@ import torch.nn as nn
 
 from . import _lib
 from .gru import ConvGRU
+from .upsample import UpmaskSource
 
 ACTS = {"none": 0, "sigmoid": 1, "softplus": 2}   # DBA_UPD_ACT_* of include/dba_hip.h
 _DTYPES = {torch.float32: _lib.DBA_F32, torch.float16: _lib.DBA_F16}
@@ -175,6 +185,57 @@ def clear_cast_cache(module):
         m.__dict__.pop("_dba_cast", None)
 
 
+PLAN_MAX_EDGES = 8192    # per list, the limit of dbaf_amd.factors
+plan_stats = dict(launches=0, host_reads=0)   # of frame_plan since import, as dbaf_amd.update_inputs.stats
+_PLAN_MEMO = _lib.EdgeSetMemo()   # edge lists whose n_uniq is known: key (buffer,), value n_uniq
+
+
+def plan_max_rows():
+    """the most buffer rows a frame plan covers (the kernel's presence flags)"""
+    return int(_lib.load().dba_frame_plan_max_rows())
+
+
+def frame_plan(ii, buffer):
+    """`torch.unique(ii, return_inverse=True)` for an edge list over `buffer` video rows, in one launch (dba_frame_plan):
+    -> (uniq [n_uniq] int64 ascending, inverse [n] int64), byte-equal to torch's.
+
+    The FIRST call on an edge list reads the launch's result words once (one device-to-host copy) and raises ValueError if
+    an entry lies outside [0, buffer).  LATER calls on the same tensor object at the same in-place version read nothing:
+    the results are sized with the remembered n_uniq, which the launch checks against what it finds; on a mismatch (the
+    list was written behind torch's version counter) it raises a pinned host word that makes the next call raise
+    RuntimeError.  Such a call can be recorded into a hipGraph."""
+    op = "frame_plan"
+    _lib.edge_list(op, ii, "ii", None, PLAN_MAX_EDGES)
+    _lib.require(int(buffer) == buffer and 0 < int(buffer) <= plan_max_rows(), op,
+                 "buffer must be an integer in 1 .. %d, got %r" % (plan_max_rows(), buffer))
+    buffer, n, dev = int(buffer), int(ii.shape[0]), ii.device
+    lib = _lib.load()
+    c = (ctypes.c_int * 6)()
+    if lib.dba_frame_plan_poll(c):
+        _PLAN_MEMO.clear()
+        raise RuntimeError("frame_plan (MI355X): an earlier call found n_uniq = %d with %d entries out of range (first at %d) "
+                           "on the device, its results were sized for n_uniq = %d: the edge list was written without torch "
+                           "noticing" % (c[0], c[1], c[2], c[3]))
+    if n == 0:
+        return torch.empty(0, dtype=torch.int64, device=dev), torch.empty(0, dtype=torch.int64, device=dev)
+    cap = min(n, buffer)
+    expect = _PLAN_MEMO.lookup((ii,), (buffer,))
+    with torch.cuda.device(dev):
+        uniq = torch.empty(cap, dtype=torch.int64, device=dev)
+        inverse = torch.empty(n, dtype=torch.int64, device=dev)
+        res = torch.empty(4, dtype=torch.int32, device=dev)
+        _lib.check(lib.dba_frame_plan(_lib.ptr(ii), n, buffer, cap, _lib.ptr(uniq), _lib.ptr(inverse), _lib.ptr(res),
+                                      -1 if expect is None else expect, _lib.stream(dev)), "dba_frame_plan")
+        plan_stats["launches"] += 1
+        if expect is None:
+            host = res.cpu().tolist()   # the one host synchronisation of a first call
+            plan_stats["host_reads"] += 1
+            _lib.require(host[1] == 0, op, "%d entries of ii lie outside [0, %d), the first at position %d" % (host[1], buffer, host[2]))
+            expect = host[0]
+            _PLAN_MEMO.remember((ii,), (buffer,), expect)
+    return uniq[:expect], inverse
+
+
 def _scatter_mean_plain(src, ix, dim_size):
     """scatter_mean(src [b, n, ...], ix [n], dim=1) in plain torch ops, on any device"""
     out = torch.zeros((src.shape[0], dim_size) + tuple(src.shape[2:]), dtype=src.dtype, device=src.device)
@@ -184,6 +245,14 @@ def _scatter_mean_plain(src, ix, dim_size):
 
 
 class GraphAgg(nn.Module):
+    """fuse_upmask (default False): hand out an UpmaskSource in place of `upmask` where the fused route's conditions hold
+    (a contiguous float16 hidden state, nothing asking for a gradient), for dbaf_amd.upsample.upsample_disps_ to run the
+    mask's convolution inside its own launch.  plan_rows: the video buffer's rows, the range of the frame plan.
+    last_uniq: the frames of the last forward, ascending (what torch.unique(ii) gives), for the caller's statements."""
+    fuse_upmask = False
+    plan_rows = None     # None: the most the plan kernel covers
+    last_uniq = None
+
     def __init__(self):
         super().__init__()
         self.conv1 = nn.Conv2d(128, 128, 3, padding=1)
@@ -192,17 +261,26 @@ class GraphAgg(nn.Module):
         self.eta = nn.Sequential(nn.Conv2d(128, 1, 3, padding=1), GradientClip(), nn.Softplus())
         self.upmask = nn.Sequential(nn.Conv2d(128, 8 * 8 * 9, 1, padding=0))
 
+    def _plan(self, ii, plain):
+        """(uniq, inverse) of the edge list: one launch of this project and, on a standing list, no host read; the
+        statements (and a list the plan kernel does not take) keep torch.unique"""
+        if (plain or not ii.is_cuda or ii.dtype != torch.int64 or ii.dim() != 1 or not ii.is_contiguous()
+                or ii.shape[0] > PLAN_MAX_EDGES):
+            return torch.unique(ii, return_inverse=True)
+        return frame_plan(ii, plan_max_rows() if self.plan_rows is None else self.plan_rows)
+
     def _aggregate(self, net, ii, plain):
         batch, num, ch, ht, wd = net.shape
         net = net.view(batch * num, ch, ht, wd)
-        uniq, ix = torch.unique(ii, return_inverse=True)
+        uniq, ix = self._plan(ii, plain)
+        self.last_uniq = uniq
         net = self.relu(self.conv1(net))
         net = net.view(batch, num, 128, ht, wd)
         if plain:
             net = _scatter_mean_plain(net, ix, int(uniq.numel()))
         else:
             from torch_scatter import scatter_mean
-            net = scatter_mean(net, ix, dim=1)
+            net = scatter_mean(net, ix, dim=1, dim_size=int(uniq.shape[0]))   # sized by the plan: no index.max() read
         net = net.view(-1, 128, ht, wd)
         return self.relu(self.conv2(net)), batch, ht, wd
 
@@ -212,6 +290,14 @@ class GraphAgg(nn.Module):
         eta = self.eta(net).view(batch, -1, ht, wd)
         upmask = self.upmask(net).view(batch, -1, 8 * 8 * 9, ht, wd)
         return .01 * eta, upmask
+
+    def _upmask_fusable(self, net):
+        """the fused launch is half only: anything else keeps the stock convolution and the two launches"""
+        # maps whose planes are whole multiples of 4096 pixels keep the two launches: measured slower fused at 25 frames of
+        # 64x64 (144 against 136 us, profiles/upsample_fused_bench.json), faster on the three other config shapes; the
+        # supposed cause is the staging's channel stride of a power of two (8 KB), not examined further
+        return (self.fuse_upmask and net.dtype == torch.float16 and _head_fusable(self, self.upmask[0], net)
+                and net.shape[1] == 128 and (net.shape[2] * net.shape[3]) % 4096 != 0)
 
     def forward(self, net, ii):
         _require(isinstance(net, torch.Tensor) and net.is_cuda, "net must be a HIP device tensor; no CPU path")
@@ -225,6 +311,9 @@ class GraphAgg(nn.Module):
             eta = heads(Head(net, w, b, relu_in=False, act="softplus", scale=.01))[0].view(batch, -1, ht, wd)
         else:
             eta = .01 * self.eta(net).view(batch, -1, ht, wd)
+        if self._upmask_fusable(net):
+            w, b = _params(self.upmask[0], net.dtype)
+            return eta, UpmaskSource(net, w, b, uniq=self.last_uniq, batch=batch)
         upmask = self.upmask(net).view(batch, -1, 8 * 8 * 9, ht, wd)
         return eta, upmask
 
@@ -243,6 +332,20 @@ class UpdateModule(nn.Module):
                                    GradientClip())
         self.gru = ConvGRU(128, 128 + 128 + 64)
         self.agg = GraphAgg()
+
+    # the fused mask route and the frame plan are GraphAgg's: these are its switches under the operator's name
+    @property
+    def fuse_upmask(self):
+        return self.agg.fuse_upmask
+
+    @fuse_upmask.setter
+    def fuse_upmask(self, on):
+        self.agg.fuse_upmask = bool(on)
+
+    @property
+    def last_uniq(self):
+        """the frames of the last forward(upsample=True), ascending: torch.unique(ii) without the caller's own unique"""
+        return self.agg.last_uniq
 
     @staticmethod
     def _flat(net, inp, corr, flow):

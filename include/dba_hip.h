@@ -604,6 +604,33 @@ int dba_cvx_upsample_disp(const float *disps, int n_disps, const int64_t *src_ro
  * index entries outside [0,dim_size) are ignored.  No atomics: bit-identical run to run. */
 int dba_segment_reduce(const void *src, int dtype, const int64_t *index, int n, int64_t outer, int64_t inner,
                        int dim_size, int mean, void *out, dba_stream_t stream);
+/* ---- upsample mode without the mask in HBM and without torch.unique (csrc/upmask.hip) ----------------------------
+ * dba_upmask_upsample_disp: GraphAgg's `upmask = self.upmask(net)` (dbaf/droid_net.py:55-72, the 1x1 convolution of :70)
+ *   and DepthVideo.upsample (dbaf/depth_video.py:205-209) with its cvx_upsample (dbaf/droid_net.py:17-31) in ONE launch:
+ *   out[dst[f]] = cvx_upsample(disps[src[f]], W x[f] + b).  Half only.
+ *     x        [B,128,ht,wd] half: the hidden state after conv2 and its ReLU;
+ *     weight   [576,128] half (16-byte aligned), bias [576] half or NULL: the 1x1 convolution's parameters;
+ *     disps    [n_disps,ht,wd] f32; out [n_out,8ht,8wd] f32 (16-byte aligned); src_rows, dst_rows [B] int64 or NULL
+ *              (identity); frames whose rows fall outside the buffers are skipped;
+ *     mask_out [B,576,ht,wd] half or NULL: receives the mask as the stock convolution would store it (the float sum plus
+ *              the bias in float, rounded once), for every frame, skipped or not.  Must not overlap x.
+ *   The product runs on mfma_f32_16x16x32_f16; the softmax and the weighted sum are the arithmetic of
+ *   dba_cvx_upsample_disp on a half mask (one shared routine): fed this launch's mask_out, that entry point gives the same
+ *   bits.  No atomics, no host synchronisation, no allocation.
+ * dba_frame_plan: `uniq, inverse = torch.unique(ii, return_inverse=True)` (dbaf/droid_net.py:57 in GraphAgg.forward,
+ *   :55-72) in one launch of one workgroup.  ii [n] int64, buffer <= dba_frame_plan_max_rows() rows; uniq [cap] int64,
+ *   cap >= min(n, buffer): the distinct entries ascending, then -1; inverse [n] int64 (-1 for an entry outside
+ *   [0, buffer)); res [4] device ints: n_uniq, the number of entries outside [0, buffer), the first such position (-1:
+ *   none), 0.  expect >= 0: the n_uniq the caller sized its results for without reading `res`; if the launch finds
+ *   another, or an entry out of range, it raises pinned host words that dba_frame_plan_poll returns (and clears) as
+ *   out6 = {n_uniq, bad, first, expect, 0, -1}; poll touches no device. */
+int dba_upmask_upsample_disp(const void *x, const void *weight, const void *bias, const float *disps, int n_disps,
+                             const int64_t *src_rows, int B, int ht, int wd, float *out, int n_out,
+                             const int64_t *dst_rows, void *mask_out, dba_stream_t stream);
+int dba_frame_plan_max_rows(void);
+int dba_frame_plan(const int64_t *ii, int n, int buffer, int cap, int64_t *uniq, int64_t *inverse, int *res, int expect,
+                   dba_stream_t stream);
+int dba_frame_plan_poll(int *out6);
 
 /* ---- edge management of the covisibility graph (csrc/proximity.hip) ---------------------------------------------
  * dba_frame_distance_bidir: DepthVideo.distance with bidirectional=True (dbaf/depth_video.py:240-270) in one launch:
