@@ -23,6 +23,7 @@
 #include <stdint.h>
 
 #include "common.h"
+#include "gru_gates.h"
 #include "row_jobs.h"
 
 namespace dba {
@@ -35,10 +36,7 @@ struct alignas(sizeof(T) * W) GruVec {
   T e[W];
 };
 
-template <typename T>
-__device__ __forceinline__ float rnd(float x) { return (float)(T)x; }  // the end of a statement: round to the tensor dtype
-
-__device__ __forceinline__ float sigmoid_f32(float x) { return 1.0f / (1.0f + expf(-x)); }
+// rnd<T>, sigmoid_f32 and the gate statements: gru_gates.h (shared with the convolution epilogues of conv3x3.hip)
 
 // ---- pack -------------------------------------------------------------------------------------------------------------
 struct PackTable {
@@ -228,8 +226,7 @@ __global__ __launch_bounds__(GRU_THREADS) void gru_reset_kernel(T *__restrict__ 
     VT o;
 #pragma unroll
     for (int j = 0; j < W; j++) {
-      const float r = rnd<T>(sigmoid_f32(rnd<T>((float)x[u].e[j] + g)));
-      o.e[j] = (T)(r * (float)y[u].e[j]);
+      o.e[j] = gru_reset_value<T>((float)x[u].e[j], g, (float)y[u].e[j]);
       if (j + 1 < W && w.step()) g = (float)gr_e[w.plane];
     }
     *(VT *)(dst + i[u]) = o;
@@ -265,11 +262,7 @@ __global__ __launch_bounds__(GRU_THREADS) void gru_blend_kernel(const T *__restr
     VT o;
 #pragma unroll
     for (int j = 0; j < W; j++) {
-      const float z = rnd<T>(sigmoid_f32(rnd<T>((float)xz[u].e[j] + bz)));
-      const float q = rnd<T>(tanhf(rnd<T>((float)xq[u].e[j] + bq)));
-      const float h = (float)y[u].e[j];
-      const float keep = rnd<T>(rnd<T>(1.0f - z) * h);
-      o.e[j] = (T)(keep + rnd<T>(z * q));
+      o.e[j] = gru_blend_value<T>(gru_gate<T>((float)xz[u].e[j], bz), (float)xq[u].e[j], bq, (float)y[u].e[j]);
       if (j + 1 < W && w.step()) {
         bz = (float)gz_e[w.plane];
         bq = (float)gq_e[w.plane];

@@ -198,6 +198,10 @@ SYMBOLS = {
     "dba_gru_context": (c_int, [_P, _P] + [c_int] * 4 + [_P, _P]),
     "dba_gru_reset": (c_int, [_P, c_int, _P, _P, _P] + [c_int] * 4 + [_P]),
     "dba_gru_blend": (c_int, [_P] * 5 + [c_int] * 4 + [_P, _P]),
+    "dba_conv3x3_tile": (c_int, []),
+    "dba_conv3x3_f16": (c_int, [_P, c_int, _P, c_int, c_int, c_int, _P, _P] + [c_int] * 5 + [_P, _P]),
+    "dba_conv3x3_gates_f16": (c_int, [_P, c_int, _P, c_int, c_int, c_int] + [_P] * 5 + [c_int] * 4 + [_P, _P, _P]),
+    "dba_conv3x3_blend_f16": (c_int, [_P, c_int, _P, c_int, c_int, c_int] + [_P] * 5 + [c_int] * 4 + [_P, _P]),
     "dba_enc_norm": (c_int, [_P, c_int, c_int, c_float, c_int, c_int, _P, _P, _P]),
     "dba_enc_norm_skip": (c_int, [_P, _P, _P, c_int, c_int, c_float, c_int, _P, _P, _P, _P]),
     "dba_enc_relu_skip": (c_int, [_P, _P, ctypes.c_longlong, c_int, _P, _P]),

@@ -1,0 +1,216 @@
+"""3x3 convolutions of half tensors on the MI355X's matrix cores (csrc/conv3x3.hip), with the ConvGRU's gate arithmetic in
+the epilogue.  Opt-in: ConvGRU.fuse_conv / UpdateModule.fuse_conv route through here, nothing else does.
+
+  pack_weights(conv_or_convs)        the parameters of one nn.Conv2d(C_in, C_out, 3, padding=1), or of several with one C_in
+                                     one behind the other along C_out, as the kernels read them: Packed(w [9, C_out, C_in]
+                                     half, tap-major, and bias [C_out] half or None).  Kept on the (first) module and rebuilt
+                                     when a parameter's data_ptr() or _version changes; never rebuilt per call
+  conv3x3(x, weight, bias, relu=False, x1=None, x1_first=0, x1_channels=None, out=None)
+                                     F.conv2d(cat([x, x1[:, x1_first:x1_first + x1_channels]], 1), weight, bias, padding=1),
+                                     optionally with torch.relu behind it; the cat is never written.  weight: a Packed or
+                                     the module's [C_out, C_in, 3, 3] (then packed on the spot, not kept)
+  conv3x3_gates(x, packed, gz, gr, net, ...)       -> (z, r * net): convz, convr and reset in one launch
+  conv3x3_blend(x, packed, gq, z, net, ..., out)   -> (1 - z) net + z tanh(convq(.) + gq): convq and blend in one launch
+  supported(c0, c1, c_out)           the kernels' channel constraints: c0 % 32 == 0, c1 % 32 == 0, c_out % 64 == 0
+
+Numerics: a float32 sum in one fixed order, plus the bias in float32, rounded ONCE to half; the gate statements behind it
+round as dbaf_amd.gru.reset_ / blend do.  MIOpen's half convolution rounds differently, so results differ from nn.Conv2d's
+in last half bits: the yardstick is the float64 statement (tests/conv3x3_cases.py).
+
+Arguments are checked on the host without synchronising; work is enqueued on torch.cuda.current_stream(), memory comes from
+torch's allocator only, and every call can be captured into a hipGraph.  CPU tensors raise.
+"""
+import collections
+import ctypes
+
+import torch
+import torch.nn as nn
+
+from . import _lib
+
+Packed = collections.namedtuple("Packed", "w bias")
+
+
+def _require(cond, msg):
+    if not cond:
+        raise ValueError("conv3x3 (MI355X): " + msg)
+
+
+def supported(c0, c1, c_out):
+    return c0 > 0 and c0 % 32 == 0 and c1 >= 0 and c1 % 32 == 0 and c_out > 0 and c_out % 64 == 0
+
+
+def tile():
+    """the side of a workgroup's square pixel tile"""
+    return int(_lib.load().dba_conv3x3_tile())
+
+
+def _pack(weights, biases):
+    w = torch.cat([t.detach() for t in weights], 0) if len(weights) > 1 else weights[0].detach()
+    w = w.permute(2, 3, 0, 1).reshape(9, w.shape[0], w.shape[1]).to(torch.float16).contiguous()
+    if all(b is None for b in biases):
+        return Packed(w, None)
+    _require(all(b is not None for b in biases), "concatenated convolutions must all have a bias, or none")
+    b = torch.cat([t.detach() for t in biases], 0) if len(biases) > 1 else biases[0].detach()
+    return Packed(w, b.to(torch.float16).contiguous())
+
+
+def pack_weights(conv_or_convs):
+    """-> Packed for one nn.Conv2d or a tuple of them (then concatenated along C_out).  The packed copy lives on the first
+    module and is rebuilt when any parameter's data_ptr() or _version changed (optimizer steps, load_state_dict, copy_); a
+    write through `.data` changes neither: call clear_pack_cache(module) after one.  During a stream capture nothing is
+    kept (the copy would live in the graph's pool) unless an eager call has packed before."""
+    convs = (conv_or_convs,) if isinstance(conv_or_convs, nn.Module) else tuple(conv_or_convs)
+    _require(len(convs) >= 1 and all(isinstance(m, nn.Conv2d) for m in convs), "pack_weights takes nn.Conv2d modules")
+    for m in convs:
+        _require(m.kernel_size == (3, 3) and m.stride == (1, 1) and m.padding == (1, 1) and m.dilation == (1, 1)
+                 and m.groups == 1 and m.padding_mode == "zeros", "only 3x3, stride 1, zero padding 1, one group")
+        _require(m.weight.is_cuda, "parameters must be on a HIP device; no CPU path")
+        _require(m.in_channels == convs[0].in_channels, "concatenated convolutions must share C_in")
+    ids = tuple(id(m) for m in convs)
+    key = tuple((m.weight.data_ptr(), m.weight._version) + ((None, None) if m.bias is None else
+                                                            (m.bias.data_ptr(), m.bias._version)) for m in convs)
+    slot = convs[0].__dict__.get("_dba_conv3x3", {})     # one entry per group of modules this one leads
+    kept = slot.get(ids)
+    if kept is None or kept[0] != key:
+        kept = (key, _pack([m.weight for m in convs], [m.bias for m in convs]))
+        if not torch.cuda.is_current_stream_capturing():
+            convs[0].__dict__.setdefault("_dba_conv3x3", slot)[ids] = kept
+    return kept[1]
+
+
+def clear_pack_cache(module):
+    for m in module.modules():
+        m.__dict__.pop("_dba_conv3x3", None)
+
+
+def _half4(t, nm, dev=None):
+    _require(isinstance(t, torch.Tensor) and t.is_cuda, "%s must be a HIP device tensor; no CPU path" % nm)
+    _require(dev is None or t.device == dev, "%s must be on %s, got %s" % (nm, dev, t.device))
+    _require(t.dtype == torch.float16, "%s must be float16, got %s" % (nm, t.dtype))
+    _require(t.dim() == 4 and t.numel() > 0 and t.is_contiguous(), "%s must be a non-empty contiguous [n, c, h, w], got %s"
+             % (nm, tuple(t.shape)))
+
+
+def _overlap(x, y):
+    a, b = x.data_ptr(), y.data_ptr()
+    return a < b + y.numel() * y.element_size() and b < a + x.numel() * x.element_size()
+
+
+def _inputs(x, weight, bias, x1, x1_first, x1_channels, c_out_of=None):
+    """the checks every entry shares -> (Packed, n, h, w, c0, c1, c1_total, first, c_out)"""
+    _half4(x, "x")
+    n, c0, h, w = (int(s) for s in x.shape)
+    c1 = c1_total = first = 0
+    if x1 is not None:
+        _half4(x1, "x1", x.device)
+        _require(x1.shape[0] == n and tuple(x1.shape[2:]) == (h, w), "x1 must be [%d, c, %d, %d], got %s" % (n, h, w, tuple(x1.shape)))
+        c1_total, first = int(x1.shape[1]), int(x1_first)
+        c1 = c1_total - first if x1_channels is None else int(x1_channels)
+        _require(first >= 0 and c1 > 0 and first + c1 <= c1_total,
+                 "x1 channels %d .. %d lie outside its %d" % (first, first + c1, c1_total))
+    if isinstance(weight, Packed):
+        pk = weight if bias is None else Packed(weight.w, bias)
+    else:
+        _require(isinstance(weight, torch.Tensor) and weight.is_cuda and weight.dim() == 4 and tuple(weight.shape[2:]) == (3, 3),
+                 "weight must be a Packed or a device tensor [C_out, C_in, 3, 3]")
+        pk = _pack([weight], [bias])
+    _require(pk.w.is_cuda and pk.w.device == x.device and pk.w.dtype == torch.float16 and pk.w.is_contiguous()
+             and pk.w.dim() == 3 and pk.w.shape[0] == 9, "packed weights must be a contiguous half [9, C_out, C_in] on %s" % x.device)
+    c_out = int(pk.w.shape[1])
+    _require(int(pk.w.shape[2]) == c0 + c1, "the weights read %d channels, the input has %d + %d" % (pk.w.shape[2], c0, c1))
+    _require(pk.w.data_ptr() % 16 == 0, "packed weights must be 16-byte aligned")
+    if pk.bias is not None:
+        _require(pk.bias.is_cuda and pk.bias.device == x.device and pk.bias.dtype == torch.float16 and pk.bias.is_contiguous()
+                 and tuple(pk.bias.shape) == (c_out,), "bias must be a contiguous half [%d] on %s" % (c_out, x.device))
+    _require(supported(c0, c1, c_out), "channels must satisfy c0 %% 32 == 0, c1 %% 32 == 0, C_out %% 64 == 0; got %d, %d, %d"
+             % (c0, c1, c_out))
+    _require(h * w * max(c0 + c1, c1_total, c_out) < 2 ** 31, "one image's planes must stay below 2^31 elements")
+    return pk, n, h, w, c0, c1, c1_total, first, c_out
+
+
+def _src_args(x, c0, x1, c1, c1_total, first):
+    return (ctypes.c_void_p(x.data_ptr()), c0, ctypes.c_void_p(x1.data_ptr()) if x1 is not None else None, c1, c1_total, first)
+
+
+def _p(t):
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _no_clobber(out, nm, x, x1, pk):
+    for t, tnm in ((x, "x"), (x1, "x1"), (pk.w, "the weights"), (pk.bias, "the bias")):
+        _require(t is None or not _overlap(out, t), "%s overlaps %s" % (nm, tnm))
+
+
+def conv3x3(x, weight, bias=None, relu=False, x1=None, x1_first=0, x1_channels=None, out=None):
+    pk, n, h, w, c0, c1, c1_total, first, c_out = _inputs(x, weight, bias, x1, x1_first, x1_channels)
+    if out is None:
+        out = torch.empty((n, c_out, h, w), dtype=torch.float16, device=x.device)
+    else:
+        _half4(out, "out", x.device)
+        _require(tuple(out.shape) == (n, c_out, h, w), "out must be %s, got %s" % ((n, c_out, h, w), tuple(out.shape)))
+        _no_clobber(out, "out", x, x1, pk)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().dba_conv3x3_f16(*_src_args(x, c0, x1, c1, c1_total, first), _p(pk.w), _p(pk.bias), c_out, n, h, w,
+                                               int(bool(relu)), _p(out), _lib.stream(x.device)), "dba_conv3x3_f16")
+    return out
+
+
+def _gate_term(g, nm, x, n, c):
+    _require(isinstance(g, torch.Tensor) and g.is_cuda and g.device == x.device and g.dtype == torch.float16
+             and g.is_contiguous() and g.numel() == n * c and g.dim() >= 2 and tuple(g.shape[:2]) == (n, c),
+             "%s must be a contiguous half [%d, %d, 1, 1] on %s" % (nm, n, c, x.device))
+
+
+def conv3x3_gates(x, packed, gz, gr, net, x1=None, x1_first=0, x1_channels=None):
+    """packed: pack_weights((convz, convr)).  -> (z, rnet) = (sigmoid(convz(.) + gz), sigmoid(convr(.) + gr) * net), new
+    tensors [n, c, h, w]"""
+    pk, n, h, w, c0, c1, c1_total, first, c_out = _inputs(x, packed, None, x1, x1_first, x1_channels)
+    c = c_out // 2
+    _half4(net, "net", x.device)
+    _require(tuple(net.shape) == (n, c, h, w), "net must be %s, got %s" % ((n, c, h, w), tuple(net.shape)))
+    _gate_term(gz, "gz", x, n, c)
+    _gate_term(gr, "gr", x, n, c)
+    z, rnet = torch.empty_like(net), torch.empty_like(net)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().dba_conv3x3_gates_f16(*_src_args(x, c0, x1, c1, c1_total, first), _p(pk.w), _p(pk.bias), _p(gz),
+                                                     _p(gr), _p(net), c, n, h, w, _p(z), _p(rnet), _lib.stream(x.device)),
+                   "dba_conv3x3_gates_f16")
+    return z, rnet
+
+
+def conv3x3_blend(x, packed, gq, z, net, x1=None, x1_first=0, x1_channels=None, out=None):
+    """packed: pack_weights(convq).  -> (1 - z) * net + z * tanh(convq(.) + gq); out may be net (in place)"""
+    pk, n, h, w, c0, c1, c1_total, first, c = _inputs(x, packed, None, x1, x1_first, x1_channels)
+    for t, nm in ((net, "net"), (z, "z")):
+        _half4(t, nm, x.device)
+        _require(tuple(t.shape) == (n, c, h, w), "%s must be %s, got %s" % (nm, (n, c, h, w), tuple(t.shape)))
+    _gate_term(gq, "gq", x, n, c)
+    if out is None:
+        out = torch.empty_like(net)
+    else:
+        _half4(out, "out", x.device)
+        _require(tuple(out.shape) == (n, c, h, w), "out must be %s, got %s" % ((n, c, h, w), tuple(out.shape)))
+        _no_clobber(out, "out", x, x1, pk)
+        _require(not _overlap(out, z) and not _overlap(out, gq), "out overlaps z or gq")
+        _require(out.data_ptr() == net.data_ptr() or not _overlap(out, net), "out overlaps net without being net")
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().dba_conv3x3_blend_f16(*_src_args(x, c0, x1, c1, c1_total, first), _p(pk.w), _p(pk.bias), _p(gq),
+                                                     _p(z), _p(net), c, n, h, w, _p(out), _lib.stream(x.device)),
+                   "dba_conv3x3_blend_f16")
+    return out
+
+
+def conv_fusable(conv, x):
+    """the fuse_conv route's facts for one nn.Conv2d on x: a contiguous half device tensor, a plain 3x3 / padding 1
+    convolution that would answer in half, channels the kernels take"""
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float16 and x.dim() == 4 and x.is_contiguous()
+            and x.numel() > 0):
+        return False
+    want = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled() else conv.weight.dtype
+    if want != torch.float16 or not conv.weight.is_cuda or conv.weight.device != x.device:
+        return False
+    if (conv.kernel_size != (3, 3) or conv.stride != (1, 1) or conv.padding != (1, 1) or conv.dilation != (1, 1)
+            or conv.groups != 1 or conv.padding_mode != "zeros"):
+        return False
+    return supported(conv.in_channels, 0, conv.out_channels) and x.shape[1] == conv.in_channels

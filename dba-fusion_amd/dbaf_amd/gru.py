@@ -21,6 +21,11 @@ float32), the convolutions answer in that dtype and nothing asks for a gradient 
 parameter requires one); otherwise it runs forward_statements, the reference's chain in plain torch ops.  CPU tensors
 raise.  Inputs are checked on the host without synchronising; work is enqueued on torch.cuda.current_stream(), memory
 comes from torch's allocator only, and a forward can be captured into a hipGraph.
+
+ConvGRU.fuse_conv (class attribute, default False: then nothing changes).  Set, and with half tensors whose channel counts
+dbaf_amd.conv takes, the fused route's three gate convolutions leave MIOpen: convz + convr + reset_ become one launch and
+convq + blend another (csrc/conv3x3.hip), five steps in all: pack, w(net) + context, the three *_glo 1x1s, GATES, BLEND.
+Results then differ from the default route in last half bits (a float32 sum rounded once against MIOpen's half convolution).
 """
 import ctypes
 
@@ -28,6 +33,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from . import conv as _conv
 
 MAX_SOURCES = 8
 _DTYPES = {torch.float32: _lib.DBA_F32, torch.float16: _lib.DBA_F16}
@@ -164,6 +170,11 @@ _CONVS = (("convz", True, 3), ("convr", True, 3), ("convq", True, 3), ("w", Fals
 
 
 class ConvGRU(nn.Module):
+    # fuse_conv (default False: then nothing changes): on the fused route with half tensors and channel counts the kernels of
+    # dbaf_amd.conv take, convz + convr + reset_ become ONE launch and convq + blend another (csrc/conv3x3.hip); cz, cr, cq
+    # and the in-place reset_ no longer exist.  Results differ from the MIOpen route in last half bits (dbaf_amd.conv).
+    fuse_conv = False
+
     def __init__(self, h_planes=128, i_planes=128):
         super().__init__()
         for name, with_inputs, k in _CONVS:
@@ -197,6 +208,13 @@ class ConvGRU(nn.Module):
             return False
         return True
 
+    def _conv_route(self, net, net_inp, gz):
+        """the facts of the fuse_conv route beyond _fusable: half tensors, the three gate convolutions answering in half,
+        channel counts the kernels take"""
+        c, ct = net.shape[1], net_inp.shape[1]
+        return (net.dtype == torch.float16 and gz.dtype == torch.float16 and _conv.supported(ct, 0, 2 * c)
+                and _conv.supported(c, ct - c, c) and all(_conv.conv_fusable(m, net_inp) for m in (self.convz, self.convr, self.convq)))
+
     def forward(self, net, *inputs):
         return self._forward(net, tuple(inputs), ())
 
@@ -223,6 +241,11 @@ class ConvGRU(nn.Module):
         glo = context(a, net)
 
         gz, gr, gq = self.convz_glo(glo), self.convr_glo(glo), self.convq_glo(glo)
+        if self.fuse_conv and self._conv_route(net, net_inp, gz):
+            c = net.shape[1]
+            z, rnet = _conv.conv3x3_gates(net_inp, _conv.pack_weights((self.convz, self.convr)), gz, gr, net)
+            return _conv.conv3x3_blend(rnet, _conv.pack_weights(self.convq), gq, z, net, x1=net_inp, x1_first=c,
+                                       x1_channels=net_inp.shape[1] - c)
         cz = self.convz(net_inp)
         cr = self.convr(net_inp)
         reset_(net_inp, cr, gr, net)    # net_inp is cat([r*net, inp], 1) from here on; convz and convr are enqueued

@@ -32,6 +32,11 @@ off: then nothing changes) and a half hidden state, the fifth return value is an
 1x1 convolution, not its result -- which dbaf_amd.upsample.upsample_disps_ consumes in ONE launch (dba_upmask_upsample_disp);
 `.materialize()` gives the stock convolution's tensor to a caller that wants it.  Float32 modules, a gradient, a
 non-contiguous state keep the two launches.
+
+fuse_conv (default off: then nothing changes) forwards to the GRU (ConvGRU.fuse_conv) and routes corr_encoder[2],
+flow_encoder[2] (their ReLUs stay deferred into pack) and GraphAgg.conv1 / conv2 (ReLU in the epilogue) through
+dbaf_amd.conv.conv3x3 where its conditions hold.  The heads' first convolutions stay on MIOpen: the heads kernel consumes
+them in a layout of its own.
 """
 import ctypes
 
@@ -39,6 +44,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from . import conv as _conv
 from .gru import ConvGRU
 from .upsample import UpmaskSource
 
@@ -250,6 +256,7 @@ class GraphAgg(nn.Module):
     mask's convolution inside its own launch.  plan_rows: the video buffer's rows, the range of the frame plan.
     last_uniq: the frames of the last forward, ascending (what torch.unique(ii) gives), for the caller's statements."""
     fuse_upmask = False
+    fuse_conv = False    # conv1 / conv2 with their ReLUs through dbaf_amd.conv.conv3x3 where its conditions hold
     plan_rows = None     # None: the most the plan kernel covers
     last_uniq = None
 
@@ -274,7 +281,7 @@ class GraphAgg(nn.Module):
         net = net.view(batch * num, ch, ht, wd)
         uniq, ix = self._plan(ii, plain)
         self.last_uniq = uniq
-        net = self.relu(self.conv1(net))
+        net = self._conv_relu(self.conv1, net, plain)
         net = net.view(batch, num, 128, ht, wd)
         if plain:
             net = _scatter_mean_plain(net, ix, int(uniq.numel()))
@@ -282,7 +289,12 @@ class GraphAgg(nn.Module):
             from torch_scatter import scatter_mean
             net = scatter_mean(net, ix, dim=1, dim_size=int(uniq.shape[0]))   # sized by the plan: no index.max() read
         net = net.view(-1, 128, ht, wd)
-        return self.relu(self.conv2(net)), batch, ht, wd
+        return self._conv_relu(self.conv2, net, plain), batch, ht, wd
+
+    def _conv_relu(self, conv, x, plain):
+        if not plain and self.fuse_conv and _conv.conv_fusable(conv, x) and not _asks_gradient(self, (x,)):
+            return _conv.conv3x3(x, _conv.pack_weights(conv), relu=True)
+        return self.relu(conv(x))
 
     def forward_statements(self, net, ii):
         """the reference's chain in plain torch ops, on any device"""
@@ -342,6 +354,23 @@ class UpdateModule(nn.Module):
     def fuse_upmask(self, on):
         self.agg.fuse_upmask = bool(on)
 
+    # the 3x3 convolutions on the matrix cores (dbaf_amd.conv): the GRU's gates, corr_encoder[2], flow_encoder[2] and the
+    # aggregation's conv1 / conv2; the heads' first convolutions stay on MIOpen
+    @property
+    def fuse_conv(self):
+        return self.gru.fuse_conv
+
+    @fuse_conv.setter
+    def fuse_conv(self, on):
+        self.gru.fuse_conv = bool(on)
+        self.agg.fuse_conv = bool(on)
+
+    def _conv3(self, conv, x, asks):
+        """conv(x) without a ReLU: through conv3x3 under fuse_conv where its conditions hold"""
+        if self.fuse_conv and not asks and _conv.conv_fusable(conv, x):
+            return _conv.conv3x3(x, _conv.pack_weights(conv), relu=False)
+        return conv(x)
+
     @property
     def last_uniq(self):
         """the frames of the last forward(upsample=True), ascending: torch.unique(ii) without the caller's own unique"""
@@ -384,8 +413,8 @@ class UpdateModule(nn.Module):
 
         # the encoders without their last ReLU; the GRU's pack applies it while it copies
         ce, fe = self.corr_encoder, self.flow_encoder
-        corr = ce[2](ce[1](ce[0](corr)))
-        flow = fe[2](fe[1](fe[0](flow)))
+        corr = self._conv3(ce[2], ce[1](ce[0](corr)), asks)
+        flow = self._conv3(fe[2], fe[1](fe[0](flow)), asks)
         if (not asks and _dense(net) and corr.dtype == net.dtype and flow.dtype == net.dtype and inp.dtype == net.dtype
                 and inp.is_contiguous()):
             net = self.gru.forward_relu(net, (inp, corr, flow), relu=(False, True, True))

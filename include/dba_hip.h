@@ -966,6 +966,33 @@ int dba_gru_reset(void *buf, int c_total, const void *cr, const void *gr, const 
 int dba_gru_blend(const void *cz, const void *gz, const void *cq, const void *gq, const void *net, int n, int c, int hw,
                   int dtype, void *out, dba_stream_t stream);
 
+/* ---- 3x3 convolutions on the matrix cores, with the ConvGRU's gates in the epilogue (csrc/conv3x3.hip) ------------------
+ * nn.Conv2d(C_in, C_out, 3, padding=1) on half tensors [n, C, h, w]: implicit GEMM on mfma_f32_16x16x32_f16, float32
+ * accumulation in one fixed order (no atomics: the same bits on every run), then c = half(acc + float(bias)), ONE rounding.
+ *   input    C_in = c0 + c1 channels from two sources: channels [0, c0) are src0 [n, c0, h, w], channels [c0, c0 + c1) are
+ *            the channels src1_first .. + c1 of src1 [n, c1_total, h, w].  c1 == 0: src0 alone (src1 is not read).
+ *   weight   [9][C_out][C_in] half, tap-major (tap = 3 ky + kx): weight.permute(2, 3, 0, 1) of the module's [C_out, C_in, 3,
+ *            3], 16-byte aligned.  bias [C_out] half or NULL.
+ * dba_conv3x3_f16: out [n, c_out, h, w] = c, or torch.relu(c) when relu != 0.
+ * dba_conv3x3_gates_f16: C_out = 2c, the weights and biases of convz then convr one behind the other; gz, gr [n, c], net
+ *   [n, c, h, w].  z_out = h(sigmoid(h(c_z + gz))); rnet_out = h(h(sigmoid(h(c_r + gr))) * net): convz, convr and
+ *   dba_gru_reset in one launch, with dba_gru_reset's and dba_gru_blend's statements (one shared routine).  Neither output
+ *   may share a byte with an input: neighbouring workgroups read every input channel with a halo.
+ * dba_conv3x3_blend_f16: C_out = c; gq [n, c], z, net [n, c, h, w].  out = h(h(h(1 - z) * net) + h(z * q)), q =
+ *   h(tanh(h(c_q + gq))): convq and dba_gru_blend in one launch.  out == net is allowed, any other overlap is not.
+ * Refused without a launch, DBA_ERR_ARG: c0 % 32, c1 % 32 or C_out % 64 not 0, an extent <= 0, src1_first + c1 > c1_total, a
+ * null pointer, a weight that is not 16-byte aligned, h * w * channels of one image or the grid beyond 2^31 - 1, an output
+ * that shares a byte with an input.  dba_conv3x3_tile: the side of a workgroup's square pixel tile. */
+int dba_conv3x3_tile(void);
+int dba_conv3x3_f16(const void *src0, int c0, const void *src1, int c1, int c1_total, int src1_first, const void *weight,
+                    const void *bias, int c_out, int n, int h, int w, int relu, void *out, dba_stream_t stream);
+int dba_conv3x3_gates_f16(const void *src0, int c0, const void *src1, int c1, int c1_total, int src1_first,
+                          const void *weight, const void *bias, const void *gz, const void *gr, const void *net, int c, int n,
+                          int h, int w, void *z_out, void *rnet_out, dba_stream_t stream);
+int dba_conv3x3_blend_f16(const void *src0, int c0, const void *src1, int c1, int c1_total, int src1_first,
+                          const void *weight, const void *bias, const void *gq, const void *z, const void *net, int c, int n,
+                          int h, int w, void *out, dba_stream_t stream);
+
 /* ---- Encoder glue (csrc/extractor.hip) -----------------------------------------------------------------------------
  * What the feature and context encoders (dbaf/modules/extractor.py:47-55, :183-198) and their caller
  * (dbaf/motion_filter.py:29-30, :35-36, :64-65) run between the convolutions, which stay with the caller.  Tensors are
