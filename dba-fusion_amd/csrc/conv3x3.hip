@@ -1,6 +1,7 @@
 // 3x3 convolutions (stride 1, zero padding 1) of half tensors in the modules' NCHW layout on the matrix cores, with the
 // ConvGRU's gate arithmetic in the epilogue (include/dba_hip.h "3x3 convolutions"):
 //   dba_conv3x3_f16        <- nn.Conv2d(C_in, C_out, 3, padding=1)(x), optionally torch.relu behind it
+//   dba_conv3x3_pair_f16   <- two such convolutions of one input, each into a tensor of its own (the heads' delta[0], weight[0])
 //   dba_conv3x3_gates_f16  <- z = sigmoid(convz(x) + gz); r = sigmoid(convr(x) + gr); r * net       (dbaf/modules/gru.py:27-29)
 //   dba_conv3x3_blend_f16  <- q = tanh(convq(cat([r*net, inp])) + gq); (1 - z) * net + z * q          (gru.py:29-31)
 //
@@ -28,6 +29,7 @@
 //     the same inputs give the same bits on every run;
 //   - epilogue: c = half(acc + float(bias)), ONE rounding (what a stock half convolution stores), then per variant
 //       BIAS   out = c or relu(c) (torch.relu on the bits: NaN stays, -0 -> +0)
+//       PAIR   BIAS with C_out = 2c written as two tensors [n, c, h, w]: channels < c -> out, channels >= c -> out2
 //       GATES  channels < c: z = gru_gate(c, gz) -> z_out; channels >= c: gru_reset_value(c, gr, net) -> rnet_out
 //       BLEND  out = gru_blend_value(z, c, gq, net); out may be net (a lane reads its own element before it writes it)
 //     with the statements of gru_gates.h, the ones gru.hip's kernels evaluate.  A lane holds 4 consecutive channels of one
@@ -54,17 +56,17 @@ constexpr int CV_THREADS = 256;
 constexpr int CV_ITEMS = CV_HP * (CV_KC / 8);                            // (pixel, 8 channels) items of a chunk
 constexpr int CV_STAGE = (CV_ITEMS + CV_THREADS - 1) / CV_THREADS;       // per thread: 6
 
-enum { CV_BIAS = 0, CV_GATES = 1, CV_BLEND = 2 };
+enum { CV_BIAS = 0, CV_GATES = 1, CV_BLEND = 2, CV_PAIR = 3 };
 
 struct ConvArgs {
   const half_t *src0, *src1;   // [n, c0, h, w]; [n, c1_total, h, w], channels src1_first .. + c1
   int c0, c1, c1_total, src1_first;
   const half_t *w, *bias;      // [9][c_out][c0 + c1]; [c_out] or null
   int c_out, n, h, wd, tiles_x, tiles;
-  half_t *out, *out2;          // BIAS, BLEND: out; GATES: z_out, rnet_out
+  half_t *out, *out2;          // BIAS, BLEND: out; GATES: z_out, rnet_out; PAIR: the two halves of c_out
   const half_t *g0, *g1;       // GATES: gz, gr [n, c]; BLEND: gq [n, c_out]
   const half_t *z, *net;       // BLEND: z; GATES, BLEND: net
-  int c, relu;                 // GATES: the gates' channels (c_out = 2c); BIAS: relu
+  int c, relu;                 // GATES, PAIR: the channels of one output (c_out = 2c); BIAS, PAIR: relu
 };
 
 template <int MT, int EPI>
@@ -169,6 +171,10 @@ __global__ __launch_bounds__(CV_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
         if (EPI == CV_BIAS) {
           const float cf = (float)c;
           a.out[((size_t)img * a.c_out + co) * HW + pix] = (a.relu && cf <= 0.f) ? (half_t)0.f : c;
+        } else if (EPI == CV_PAIR) {
+          const float cf = (float)c;
+          half_t *dst = co < a.c ? a.out + ((size_t)img * a.c + co) * HW : a.out2 + ((size_t)img * a.c + (co - a.c)) * HW;
+          dst[pix] = (a.relu && cf <= 0.f) ? (half_t)0.f : c;
         } else if (EPI == CV_GATES) {
           if (co < a.c) {
             a.out[((size_t)img * a.c + co) * HW + pix] = (half_t)gru_gate<half_t>((float)c, gt[m][i]);
@@ -263,6 +269,22 @@ int dba_conv3x3_f16(const void *src0, int c0, const void *src1, int c1, int c1_t
   a.out = (half_t *)out;
   a.relu = relu != 0;
   return cv_launch<CV_BIAS>(a, (hipStream_t)stream);
+}
+
+int dba_conv3x3_pair_f16(const void *src0, int c0, const void *src1, int c1, int c1_total, int src1_first, const void *weight,
+                         const void *bias, int c, int n, int h, int w, int relu, void *out0, void *out1, dba_stream_t stream) {
+  if (c <= 0 || c > INT32_MAX / 2) return DBA_ERR_ARG;
+  ConvArgs a{};
+  const int rc = cv_input(a, src0, c0, src1, c1, c1_total, src1_first, weight, bias, 2 * c, n, h, w);
+  if (rc != DBA_OK) return rc;
+  if (!out0 || !out1 || (((uintptr_t)out0 | (uintptr_t)out1) & 1)) return DBA_ERR_ARG;
+  const size_t bytes = (size_t)n * c * h * w * 2;
+  if (cv_clobbers(a, out0, c) || cv_clobbers(a, out1, c) || cv_overlaps(out0, bytes, out1, bytes)) return DBA_ERR_ARG;
+  a.out = (half_t *)out0;
+  a.out2 = (half_t *)out1;
+  a.c = c;
+  a.relu = relu != 0;
+  return cv_launch<CV_PAIR>(a, (hipStream_t)stream);
 }
 
 int dba_conv3x3_gates_f16(const void *src0, int c0, const void *src1, int c1, int c1_total, int src1_first,

@@ -11,7 +11,18 @@ the epilogue.  Opt-in: ConvGRU.fuse_conv / UpdateModule.fuse_conv route through 
                                      the module's [C_out, C_in, 3, 3] (then packed on the spot, not kept)
   conv3x3_gates(x, packed, gz, gr, net, ...)       -> (z, r * net): convz, convr and reset in one launch
   conv3x3_blend(x, packed, gq, z, net, ..., out)   -> (1 - z) net + z tanh(convq(.) + gq): convq and blend in one launch
+  conv3x3_pair(x, packed, relu=False)              -> (conv_a(x), conv_b(x)) for pack_weights((conv_a, conv_b)): one launch,
+                                     two contiguous tensors (the heads' delta[0] / weight[0])
   supported(c0, c1, c_out)           the kernels' channel constraints: c0 % 32 == 0, c1 % 32 == 0, c_out % 64 == 0
+
+and the 1x1 convolutions as a GEMM on the same matrix instruction (csrc/conv1x1.hip); C_in any positive count, C_out % 64 == 0:
+
+  pack_pointwise(conv_or_convs)      Pointwise(w [C_out, ceil32(C_in)] half with a zero tail, bias, c_in), cached as above
+  conv1x1(x, weight, bias=None, relu=False, out=None)
+                                     F.conv2d(x, weight, bias) for a 1x1 weight, optionally torch.relu behind it
+  conv1x1_context(net, packed_w, packed_glo)       -> (glo, gz, gr, gq): w(net), the ConvGRU's context mean and the three
+                                     *_glo 1x1s in two launches; w(net) is never written
+  conv_fusable / pointwise_fusable   the routing facts of one nn.Conv2d on x
 
 Numerics: a float32 sum in one fixed order, plus the bias in float32, rounded ONCE to half; the gate statements behind it
 round as dbaf_amd.gru.reset_ / blend do.  MIOpen's half convolution rounds differently, so results differ from nn.Conv2d's
@@ -29,6 +40,7 @@ import torch.nn as nn
 from . import _lib
 
 Packed = collections.namedtuple("Packed", "w bias")
+Pointwise = collections.namedtuple("Pointwise", "w bias c_in")   # w [C_out, ceil32(C_in)], the columns from c_in on zero
 
 
 def _require(cond, msg):
@@ -82,6 +94,46 @@ def pack_weights(conv_or_convs):
 def clear_pack_cache(module):
     for m in module.modules():
         m.__dict__.pop("_dba_conv3x3", None)
+        m.__dict__.pop("_dba_conv1x1", None)
+
+
+def pointwise_tile():
+    """the pixels of a workgroup's tile of the 1x1 kernels"""
+    return int(_lib.load().dba_conv1x1_tile())
+
+
+def _pack_pointwise(weights, biases):
+    w = torch.cat([t.detach().flatten(1) for t in weights], 0)
+    c_out, c_in = int(w.shape[0]), int(w.shape[1])
+    wp = torch.zeros((c_out, (c_in + 31) // 32 * 32), dtype=torch.float16, device=w.device)
+    wp[:, :c_in] = w
+    if all(b is None for b in biases):
+        return Pointwise(wp, None, c_in)
+    _require(all(b is not None for b in biases), "concatenated convolutions must all have a bias, or none")
+    return Pointwise(wp, torch.cat([t.detach() for t in biases], 0).to(torch.float16).contiguous(), c_in)
+
+
+def pack_pointwise(conv_or_convs):
+    """-> Pointwise for one nn.Conv2d(C_in, C_out, 1) or a tuple of them with one C_in (then one behind the other along
+    C_out): w [C_out, ceil32(C_in)] half with a zero tail, bias [C_out] half or None, c_in.  Kept and rebuilt as
+    pack_weights keeps its copies: on the first module, under the parameters' data_ptr() and _version; nothing is kept
+    during a stream capture; clear_pack_cache forgets it."""
+    convs = (conv_or_convs,) if isinstance(conv_or_convs, nn.Module) else tuple(conv_or_convs)
+    _require(len(convs) >= 1 and all(isinstance(m, nn.Conv2d) for m in convs), "pack_pointwise takes nn.Conv2d modules")
+    for m in convs:
+        _require(_plain(m, 1), "only 1x1, stride 1, no padding, one group")
+        _require(m.weight.is_cuda, "parameters must be on a HIP device; no CPU path")
+        _require(m.in_channels == convs[0].in_channels, "concatenated convolutions must share C_in")
+    ids = tuple(id(m) for m in convs)
+    key = tuple((m.weight.data_ptr(), m.weight._version) + ((None, None) if m.bias is None else
+                                                            (m.bias.data_ptr(), m.bias._version)) for m in convs)
+    slot = convs[0].__dict__.get("_dba_conv1x1", {})
+    kept = slot.get(ids)
+    if kept is None or kept[0] != key:
+        kept = (key, _pack_pointwise([m.weight for m in convs], [m.bias for m in convs]))
+        if not torch.cuda.is_current_stream_capturing():
+            convs[0].__dict__.setdefault("_dba_conv1x1", slot)[ids] = kept
+    return kept[1]
 
 
 def _half4(t, nm, dev=None):
@@ -201,16 +253,111 @@ def conv3x3_blend(x, packed, gq, z, net, x1=None, x1_first=0, x1_channels=None, 
     return out
 
 
+def conv3x3_pair(x, packed, relu=False):
+    """packed: pack_weights((conv_a, conv_b)), two convolutions of C_in -> c.  -> (conv_a(x), conv_b(x)), new contiguous
+    tensors [n, c, h, w], each through torch.relu when relu: the two halves of conv3x3(x, packed) in ONE launch"""
+    _require(isinstance(packed, Packed), "conv3x3_pair takes pack_weights' result")
+    pk, n, h, w, c0, c1, c1_total, first, c_out = _inputs(x, packed, None, None, 0, None)
+    _require(c_out % 2 == 0, "the packed weights must hold two convolutions of one C_out")
+    c = c_out // 2
+    out0 = torch.empty((n, c, h, w), dtype=torch.float16, device=x.device)
+    out1 = torch.empty_like(out0)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().dba_conv3x3_pair_f16(*_src_args(x, c0, None, c1, c1_total, first), _p(pk.w), _p(pk.bias), c, n, h, w,
+                                                    int(bool(relu)), _p(out0), _p(out1), _lib.stream(x.device)),
+                   "dba_conv3x3_pair_f16")
+    return out0, out1
+
+
+def _pointwise(weight, bias, dev, what="weight"):
+    """a Pointwise, or the module's [C_out, C_in, 1, 1] / [C_out, C_in] (then packed on the spot, not kept), checked"""
+    if isinstance(weight, Pointwise):
+        pk = weight if bias is None else Pointwise(weight.w, bias, weight.c_in)
+    else:
+        _require(isinstance(weight, torch.Tensor) and weight.is_cuda and weight.dim() in (2, 4) and weight.numel() > 0
+                 and tuple(weight.shape[2:]) in ((), (1, 1)), "%s must be a Pointwise or a device tensor [C_out, C_in, 1, 1]" % what)
+        pk = _pack_pointwise([weight], [bias])
+    c_out = int(pk.w.shape[0]) if isinstance(pk.w, torch.Tensor) and pk.w.dim() == 2 else 0
+    _require(c_out > 0 and pk.w.is_cuda and pk.w.device == dev and pk.w.dtype == torch.float16 and pk.w.is_contiguous()
+             and 0 < pk.c_in <= pk.w.shape[1] == (pk.c_in + 31) // 32 * 32,
+             "packed %s must be a contiguous half [C_out, ceil32(C_in)] on %s" % (what, dev))
+    _require(pk.w.data_ptr() % 16 == 0, "packed %s must be 16-byte aligned" % what)
+    if pk.bias is not None:
+        _require(pk.bias.is_cuda and pk.bias.device == dev and pk.bias.dtype == torch.float16 and pk.bias.is_contiguous()
+                 and tuple(pk.bias.shape) == (c_out,), "the bias of %s must be a contiguous half [%d] on %s" % (what, c_out, dev))
+    _require(c_out % 64 == 0, "C_out must be a multiple of 64, got %d" % c_out)
+    return pk, c_out
+
+
+def conv1x1(x, weight, bias=None, relu=False, out=None):
+    """F.conv2d(x, weight, bias) for a 1x1 weight, optionally with torch.relu behind it.  x [n, C_in, h, w] half, C_in any
+    positive count; weight: a Pointwise (pack_pointwise) or the module's [C_out, C_in, 1, 1]; C_out % 64 == 0"""
+    _half4(x, "x")
+    n, c_in, h, w = (int(s) for s in x.shape)
+    pk, c_out = _pointwise(weight, bias, x.device)
+    _require(pk.c_in == c_in, "the weights read %d channels, the input has %d" % (pk.c_in, c_in))
+    _require(h * w * max(c_in, c_out) < 2 ** 31, "one image's planes must stay below 2^31 elements")
+    if out is None:
+        out = torch.empty((n, c_out, h, w), dtype=torch.float16, device=x.device)
+    else:
+        _half4(out, "out", x.device)
+        _require(tuple(out.shape) == (n, c_out, h, w), "out must be %s, got %s" % ((n, c_out, h, w), tuple(out.shape)))
+        for t, tnm in ((x, "x"), (pk.w, "the weights"), (pk.bias, "the bias")):
+            _require(t is None or not _overlap(out, t), "out overlaps %s" % tnm)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().dba_conv1x1_f16(_p(x), c_in, _p(pk.w), _p(pk.bias), c_out, n, h * w, int(bool(relu)), _p(out),
+                                               _lib.stream(x.device)), "dba_conv1x1_f16")
+    return out
+
+
+def conv1x1_context(net, packed_w, packed_glo):
+    """packed_w: pack_pointwise(gru.w); packed_glo: pack_pointwise((gru.convz_glo, gru.convr_glo, gru.convq_glo)).
+    -> (glo, gz, gr, gq), each [n, c, 1, 1] half: glo = mean_hw(sigmoid(w(net)) * net) statement by statement, gX =
+    convX_glo(glo); w(net) itself is never written.  Two launches."""
+    _half4(net, "net")
+    n, c, h, w = (int(s) for s in net.shape)
+    pk, c_out = _pointwise(packed_w, None, net.device, "w")
+    pg, cg = _pointwise(packed_glo, None, net.device, "the *_glo weights")
+    _require(pk.c_in == c and c_out == c, "w must be a 1x1 convolution of %d -> %d channels, got %d -> %d" % (c, c, pk.c_in, c_out))
+    _require(pg.c_in == c and cg == 3 * c and pg.w.shape[1] == c,
+             "the *_glo weights must be three 1x1 convolutions of %d -> %d channels one behind the other" % (c, c))
+    _require(c <= 1024, "at most 1024 channels, got %d" % c)
+    _require(h * w * c < 2 ** 31, "one image's planes must stay below 2^31 elements")
+    lib = _lib.load()
+    nbytes = int(lib.dba_conv1x1_context_workspace_bytes(n, c, h * w))
+    outs = [torch.empty((n, c, 1, 1), dtype=torch.float16, device=net.device) for _ in range(4)]
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=net.device)
+    with torch.cuda.device(net.device):
+        _lib.check(lib.dba_conv1x1_context_f16(_p(net), _p(pk.w), _p(pk.bias), _p(pg.w), _p(pg.bias), c, n, h * w, _p(ws), nbytes,
+                                               *[_p(t) for t in outs], _lib.stream(net.device)), "dba_conv1x1_context_f16")
+    return tuple(outs)
+
+
+def _plain(conv, k):
+    """a k x k convolution of stride 1 with zero padding k // 2, no dilation, one group"""
+    return (conv.kernel_size == (k, k) and conv.stride == (1, 1) and conv.padding == (k // 2, k // 2) and conv.dilation == (1, 1)
+            and conv.groups == 1 and conv.padding_mode == "zeros")
+
+
+def _answers_half(conv, dev):
+    """the convolution's parameters lie on dev and it would answer in half there"""
+    want = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled() else conv.weight.dtype
+    return want == torch.float16 and conv.weight.is_cuda and conv.weight.device == dev
+
+
+def _half_map(x):
+    return (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float16 and x.dim() == 4 and x.is_contiguous()
+            and x.numel() > 0)
+
+
 def conv_fusable(conv, x):
     """the fuse_conv route's facts for one nn.Conv2d on x: a contiguous half device tensor, a plain 3x3 / padding 1
     convolution that would answer in half, channels the kernels take"""
-    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float16 and x.dim() == 4 and x.is_contiguous()
-            and x.numel() > 0):
-        return False
-    want = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled() else conv.weight.dtype
-    if want != torch.float16 or not conv.weight.is_cuda or conv.weight.device != x.device:
-        return False
-    if (conv.kernel_size != (3, 3) or conv.stride != (1, 1) or conv.padding != (1, 1) or conv.dilation != (1, 1)
-            or conv.groups != 1 or conv.padding_mode != "zeros"):
-        return False
-    return supported(conv.in_channels, 0, conv.out_channels) and x.shape[1] == conv.in_channels
+    return (_half_map(x) and _answers_half(conv, x.device) and _plain(conv, 3)
+            and supported(conv.in_channels, 0, conv.out_channels) and x.shape[1] == conv.in_channels)
+
+
+def pointwise_fusable(conv, x):
+    """conv_fusable for a 1x1 convolution: any C_in, C_out a multiple of 64"""
+    return (_half_map(x) and _answers_half(conv, x.device) and _plain(conv, 1) and conv.out_channels % 64 == 0
+            and x.shape[1] == conv.in_channels and x.shape[2] * x.shape[3] * max(x.shape[1], conv.out_channels) < 2 ** 31)

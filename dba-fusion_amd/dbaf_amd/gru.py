@@ -24,8 +24,11 @@ comes from torch's allocator only, and a forward can be captured into a hipGraph
 
 ConvGRU.fuse_conv (class attribute, default False: then nothing changes).  Set, and with half tensors whose channel counts
 dbaf_amd.conv takes, the fused route's three gate convolutions leave MIOpen: convz + convr + reset_ become one launch and
-convq + blend another (csrc/conv3x3.hip), five steps in all: pack, w(net) + context, the three *_glo 1x1s, GATES, BLEND.
-Results then differ from the default route in last half bits (a float32 sum rounded once against MIOpen's half convolution).
+convq + blend another (csrc/conv3x3.hip).  Where w and the three *_glo are plain 1x1s of c -> c channels answering in half,
+w(net), the context and the *_glo 1x1s are the two launches of dbaf_amd.conv.conv1x1_context (csrc/conv1x1.hip; w(net) is
+never written), and the forward calls no stock convolution: pack, context (two launches), GATES, BLEND.  It then returns the
+same bytes on every call.  Results differ from the default route in last half bits (a float32 sum rounded once against
+MIOpen's half convolution).
 """
 import ctypes
 
@@ -113,8 +116,13 @@ def pack(net, *inputs, relu=()):
     return dst
 
 
-def context(a, net):
-    """a = w(net), net [n, c, h, w] -> glo [n, c, 1, 1] = mean over the plane of sigmoid(a) * net, statement by statement"""
+def context(a, net, glo_weights=None):
+    """a = w(net), net [n, c, h, w] -> glo [n, c, 1, 1] = mean over the plane of sigmoid(a) * net, statement by statement.
+    The context step of the fuse_conv route: with glo_weights = pack_pointwise((convz_glo, convr_glo, convq_glo)), `a` is
+    pack_pointwise(w) in place of w's result, and w(net), the mean and the three *_glo 1x1s are
+    dbaf_amd.conv.conv1x1_context's two launches -> (glo, gz, gr, gq); w(net) is never written (half only)."""
+    if glo_weights is not None:
+        return _conv.conv1x1_context(net, a, glo_weights)
     n, c, hw = _planes(net, "net")
     _like(a, "a", net, "net")
     glo = torch.empty((n, c) + (1,) * (net.dim() - 2), dtype=net.dtype, device=net.device)
@@ -215,6 +223,23 @@ class ConvGRU(nn.Module):
         return (net.dtype == torch.float16 and gz.dtype == torch.float16 and _conv.supported(ct, 0, 2 * c)
                 and _conv.supported(c, ct - c, c) and all(_conv.conv_fusable(m, net_inp) for m in (self.convz, self.convr, self.convq)))
 
+    def _pointwise_route(self, net, inputs):
+        """the facts of the route that calls no stock convolution, known before anything is enqueued: _conv_route's (on the
+        channel counts pack will give), and w and the three *_glo plain 1x1s of c -> c channels answering in half"""
+        c, ct, dev = net.shape[1], net.shape[1] + sum(int(x.shape[1]) for x in inputs), net.device
+        if net.dtype != torch.float16 or not (_conv.supported(ct, 0, 2 * c) and _conv.supported(c, ct - c, c)) or c > 1024:
+            return False
+        if ct * net.shape[2] * net.shape[3] >= 2 ** 31:   # one image's packed planes: the kernels' int offsets
+            return False
+        for m in (self.convz, self.convr, self.convq):
+            if not (_conv._plain(m, 3) and _conv._answers_half(m, dev) and m.in_channels == ct and m.out_channels == c):
+                return False
+        for m in (self.w, self.convz_glo, self.convr_glo, self.convq_glo):
+            if not (_conv._plain(m, 1) and _conv._answers_half(m, dev) and m.in_channels == c and m.out_channels == c):
+                return False
+        biases = [m.bias is None for m in (self.convz_glo, self.convr_glo, self.convq_glo)]
+        return all(biases) or not any(biases)
+
     def forward(self, net, *inputs):
         return self._forward(net, tuple(inputs), ())
 
@@ -230,6 +255,15 @@ class ConvGRU(nn.Module):
         for k, x in enumerate((net,) + inputs):
             _require(isinstance(x, torch.Tensor) and x.is_cuda, "%s must be a HIP device tensor; no CPU path"
                      % ("net" if k == 0 else "inputs[%d]" % (k - 1)))
+        if self.fuse_conv and self._fusable(net, inputs) and self._pointwise_route(net, inputs):
+            # no stock convolution: w(net), the context and the three *_glo 1x1s are conv1x1_context's two launches
+            c = net.shape[1]
+            net_inp = pack(net, *inputs, relu=((False,) + relu) if any(relu) else ())
+            glo, gz, gr, gq = context(_conv.pack_pointwise(self.w), net,
+                                      _conv.pack_pointwise((self.convz_glo, self.convr_glo, self.convq_glo)))
+            z, rnet = _conv.conv3x3_gates(net_inp, _conv.pack_weights((self.convz, self.convr)), gz, gr, net)
+            return _conv.conv3x3_blend(rnet, _conv.pack_weights(self.convq), gq, z, net, x1=net_inp, x1_first=c,
+                                       x1_channels=net_inp.shape[1] - c)
         a = self.w(net)
         # autocast may answer in another dtype than the inputs': then the statements' own promotion rules apply
         if not self._fusable(net, inputs) or a.dtype != net.dtype:

@@ -35,8 +35,12 @@ non-contiguous state keep the two launches.
 
 fuse_conv (default off: then nothing changes) forwards to the GRU (ConvGRU.fuse_conv) and routes corr_encoder[2],
 flow_encoder[2] (their ReLUs stay deferred into pack) and GraphAgg.conv1 / conv2 (ReLU in the epilogue) through
-dbaf_amd.conv.conv3x3 where its conditions hold.  The heads' first convolutions stay on MIOpen: the heads kernel consumes
-them in a layout of its own.
+dbaf_amd.conv.conv3x3 where its conditions hold.  corr_encoder[0] with its ReLU is one conv1x1 launch (196 channels: the
+last chunk of 32 is filled with zeros).  The heads' first convolutions delta[0] / weight[0] with their ReLUs are ONE
+conv3x3_pair launch that writes two plain contiguous [n, 128, ht, wd] tensors, which is what heads() reads (relu_in off: the
+ReLU of half(c) is the reference's in-place ReLU).  With the flag, a forward with upsample=False then makes one stock
+convolution call, the 7x7 flow stem.  Each piece routes on its own facts; where they fail, that piece alone keeps the
+stock route.
 """
 import ctypes
 
@@ -354,8 +358,8 @@ class UpdateModule(nn.Module):
     def fuse_upmask(self, on):
         self.agg.fuse_upmask = bool(on)
 
-    # the 3x3 convolutions on the matrix cores (dbaf_amd.conv): the GRU's gates, corr_encoder[2], flow_encoder[2] and the
-    # aggregation's conv1 / conv2; the heads' first convolutions stay on MIOpen
+    # the convolutions on the matrix cores (dbaf_amd.conv): the whole GRU, corr_encoder[0] / [2], flow_encoder[2], the
+    # heads' delta[0] / weight[0] and the aggregation's conv1 / conv2; the 7x7 flow stem stays on MIOpen
     @property
     def fuse_conv(self):
         return self.gru.fuse_conv
@@ -370,6 +374,15 @@ class UpdateModule(nn.Module):
         if self.fuse_conv and not asks and _conv.conv_fusable(conv, x):
             return _conv.conv3x3(x, _conv.pack_weights(conv), relu=False)
         return conv(x)
+
+    def _pair_route(self, net, asks):
+        """delta[0] and weight[0] as one conv3x3_pair: both take conv3x3's route on net, agree in their channels and biases,
+        and the heads launch behind them takes half tensors"""
+        d0, w0 = self.delta[0], self.weight[0]
+        return (self.fuse_conv and not asks and _conv.conv_fusable(d0, net) and _conv.conv_fusable(w0, net)
+                and d0.out_channels == w0.out_channels and (d0.bias is None) == (w0.bias is None)
+                and _head_fusable(self, self.delta[2], net) and _head_fusable(self, self.weight[2], net)
+                and self.delta[2].in_channels == d0.out_channels and self.weight[2].in_channels == w0.out_channels)
 
     @property
     def last_uniq(self):
@@ -413,7 +426,11 @@ class UpdateModule(nn.Module):
 
         # the encoders without their last ReLU; the GRU's pack applies it while it copies
         ce, fe = self.corr_encoder, self.flow_encoder
-        corr = self._conv3(ce[2], ce[1](ce[0](corr)), asks)
+        if self.fuse_conv and not asks and _conv.pointwise_fusable(ce[0], corr):
+            corr = _conv.conv1x1(corr, _conv.pack_pointwise(ce[0]), relu=True)
+        else:
+            corr = ce[1](ce[0](corr))
+        corr = self._conv3(ce[2], corr, asks)
         flow = self._conv3(fe[2], fe[1](fe[0](flow)), asks)
         if (not asks and _dense(net) and corr.dtype == net.dtype and flow.dtype == net.dtype and inp.dtype == net.dtype
                 and inp.is_contiguous()):
@@ -421,7 +438,15 @@ class UpdateModule(nn.Module):
         else:
             net = self.gru(net, inp, ce[3](corr), fe[3](flow))
 
-        # the heads: the two first convolutions as torch, everything behind them in one launch
+        # the heads: the two first convolutions as torch (under fuse_conv: ONE conv3x3_pair launch with their ReLUs, the
+        # reference's in-place ReLU of half(c)), everything behind them in one launch
+        if self._pair_route(net, asks):
+            hd, hw = _conv.conv3x3_pair(net, _conv.pack_weights((self.delta[0], self.weight[0])), relu=True)
+            wd_, bd = _params(self.delta[2], hd.dtype)
+            ww, bw = _params(self.weight[2], hw.dtype)
+            delta, weight = heads(Head(hd, wd_, bd, relu_in=False, act="none"), Head(hw, ww, bw, relu_in=False, act="sigmoid"))
+            delta, weight = delta.view(dim[0], dim[1], dim[3], dim[4], 2), weight.view(dim[0], dim[1], dim[3], dim[4], 2)
+            return self._result(net.view(*dim), delta, weight, self.agg, ii, upsample)
         hd, hw = self.delta[0](net), self.weight[0](net)
         if (not asks and hd.dtype == hw.dtype and _head_fusable(self, self.delta[2], hd) and _head_fusable(self, self.weight[2], hw)
                 and _dense(hw)):

@@ -992,6 +992,41 @@ int dba_conv3x3_gates_f16(const void *src0, int c0, const void *src1, int c1, in
 int dba_conv3x3_blend_f16(const void *src0, int c0, const void *src1, int c1, int c1_total, int src1_first,
                           const void *weight, const void *bias, const void *gq, const void *z, const void *net, int c, int n,
                           int h, int w, void *out, dba_stream_t stream);
+/* dba_conv3x3_pair_f16: C_out = 2c, the weights and biases of two convolutions of one input one behind the other (the heads'
+ *   delta[0] then weight[0]).  out0 [n, c, h, w] = the channels [0, c) of c, out1 [n, c, h, w] the channels [c, 2c), each
+ *   through torch.relu when relu != 0: byte for byte the two halves of dba_conv3x3_f16 on the same operands (same tile,
+ *   staging and accumulation order), written as two contiguous tensors.  Refused as dba_conv3x3_f16 refuses, and when out0
+ *   and out1 share a byte. */
+int dba_conv3x3_pair_f16(const void *src0, int c0, const void *src1, int c1, int c1_total, int src1_first, const void *weight,
+                         const void *bias, int c, int n, int h, int w, int relu, void *out0, void *out1, dba_stream_t stream);
+
+/* ---- 1x1 convolutions on the matrix cores, with the ConvGRU's context chain behind one (csrc/conv1x1.hip) ---------------
+ * nn.Conv2d(C_in, C_out, 1) on half tensors [n, C, hw] (the plane flattened): a GEMM on mfma_f32_16x16x32_f16,
+ *   c[n, o, p] = half(sum_i W[o, i] * x[n, i, p] + float(b[o])),
+ * a float32 sum in one fixed order (chunks of 32 channels ascending, the hardware's order inside an MFMA; no atomics: the same
+ * bits on every run), ONE rounding.  C_in is any positive count, C_out a multiple of 64.
+ *   weight   [C_out][Kp] half, Kp = C_in rounded up to a multiple of 32, the columns [C_in, Kp) ZERO, 16-byte aligned.  bias
+ *            [C_out] half or NULL.  No load touches an address outside x, weight and bias.
+ * dba_conv1x1_f16: out [n, c_out, hw] = c, or torch.relu(c) when relu != 0 (NaN stays, -0 -> +0).
+ * dba_conv1x1_context_f16: C_in = C_out = c <= 1024, weight / bias those of ConvGRU.w.  a = c above is never stored.
+ *   glo [n, c] = h(sum_p(h(h(sigmoid(a)) * net)) * float32(1 / hw)), dba_gru_context's statement: glo = torch.sigmoid(self.w(net))
+ *   * net; glo.view(b, c, h*w).mean(-1) (dbaf/modules/gru.py:24-25).  The float32 sum of a plane runs in ONE order: inside a tile
+ *   of dba_conv1x1_tile() pixels a lane adds the pixels r, r + 16, .. ascending and 16 lanes fold by shifts of 1, 2, 4, 8; a
+ *   second launch adds the tiles' partial sums (workspace, float32 [n, tiles, c]) in tile order.
+ *   gz, gr, gq [n, c] = half(sum_i Wg[o, i] * float(glo[n, i]) + float(bg[o])) for the rows o of glo_weight [3c][c] (convz_glo,
+ *   convr_glo, convq_glo one behind the other, 16-byte aligned) and glo_bias [3c] or NULL: a float32 sum over i ascending, ONE
+ *   rounding (:27-29's convX_glo(glo)).  Two launches in all.  workspace: at least dba_conv1x1_context_workspace_bytes(n, c, hw)
+ *   bytes, 4-byte aligned, else DBA_ERR_WORKSPACE.
+ * Refused without a launch, DBA_ERR_ARG: an extent <= 0, C_out % 64 != 0, a null or misaligned pointer, hw * channels of one
+ * image or the grid beyond 2^31 - 1, an output (or the workspace) that shares a byte with an input or with another output.
+ * dba_conv1x1_tile: the pixels of a workgroup's tile. */
+int dba_conv1x1_tile(void);
+int dba_conv1x1_f16(const void *x, int c_in, const void *weight, const void *bias, int c_out, int n, int hw, int relu, void *out,
+                    dba_stream_t stream);
+size_t dba_conv1x1_context_workspace_bytes(int n, int c, int hw);
+int dba_conv1x1_context_f16(const void *net, const void *weight, const void *bias, const void *glo_weight, const void *glo_bias,
+                            int c, int n, int hw, void *workspace, size_t workspace_bytes, void *glo, void *gz, void *gr,
+                            void *gq, dba_stream_t stream);
 
 /* ---- Encoder glue (csrc/extractor.hip) -----------------------------------------------------------------------------
  * What the feature and context encoders (dbaf/modules/extractor.py:47-55, :183-198) and their caller
