@@ -42,6 +42,13 @@ struct DeviceOnce {
 
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// [p, p + bytes) and [q, q + qbytes) share a byte; a null pointer overlaps nothing.  Callers that count bytes in long long
+// pass values they have checked to be non-negative
+inline bool ranges_overlap(const void *p, size_t bytes, const void *q, size_t qbytes) {
+  const uintptr_t x = (uintptr_t)p, y = (uintptr_t)q;
+  return p && q && x < y + qbytes && y < x + bytes;
+}
+
 // ---- wave64 cross-lane reductions with DPP ------------------------------------------------
 // Sum over the 64 lanes of a wavefront.  row_shr 1,2,4,8 fold each 16-lane row into its lane 15,
 // row_bcast:15 / row_bcast:31 carry the row totals across rows; the total lands in lane 63.

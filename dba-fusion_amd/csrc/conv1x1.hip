@@ -4,25 +4,18 @@
 //   dba_conv1x1_context_f16  <- glo = (sigmoid(w(net)) * net).view(b, c, h*w).mean(-1); convz_glo(glo), convr_glo(glo),
 //                               convq_glo(glo)                                                (dbaf/modules/gru.py:24-29)
 //
-// conv1x1_kernel<MT, EPI>.  GEMM on mfma_f32_16x16x32_f16: M = output channels (A = the packed weights), N = 16 consecutive
-// pixels of the flattened plane (B = the staged input), K = 32 input channels.
-//   - tile: one workgroup (4 waves) owns PW_P = 128 consecutive pixels of one image's plane and 64 * MT output channels (MT =
-//     2 when C_out is a multiple of 128, else 1); wave g owns the channels g * 16 * MT .. + 16 * MT of that block for all
-//     128 pixels: 8 x MT accumulator tiles of 4 floats.  blockIdx.x = image * tiles + tile, blockIdx.y = the channel block;
-//   - staging: as conv3x3.hip's.  The planes are pixel-contiguous and the MFMA wants 8 consecutive channels per lane, so the
-//     input is walked in chunks of 32 channels and a chunk's 128 pixels go through LDS transposed, into rows of 32 + 8 halves
-//     (80-byte pitch): a thread takes one pixel and 8 channels (8 guarded 2-byte loads, neighbouring threads neighbouring
-//     pixels) and writes one 16-byte LDS vector.  Pixels at or beyond hw and channels at or beyond C_in (the last chunk of a
-//     C_in that is no multiple of 32: 196) are written as zeros and never dereferenced.  One buffer (10 KB), two barriers per
-//     chunk;
-//   - fragments: B for pixel group o is lane l's 16 bytes [pixel 16 o + (l & 15)][channels 8 (l >> 4) ..], one aligned
-//     ds_read_b128; A is 16 bytes of the packed weights [C_out][Kp] (Kp = C_in rounded up to 32, the tail zero) at [channel
-//     l & 15][chunk * 32 + 8 (l >> 4)], read from L2 once per (wave, chunk) and used for the 8 pixel groups.  Both operands
-//     are zero in the tail of the last chunk, so a NaN or an infinity there cannot arise;
+// conv1x1_kernel<MT, EPI>: conv_mfma.h's GEMM with N = 16 consecutive pixels of the flattened plane.
+//   - tile: PW_P = 128 consecutive pixels of one image's plane; a wave holds 8 x MT accumulator tiles of 4 floats;
+//   - staging: a chunk's 128 pixels.  Pixels at or beyond hw and channels at or beyond C_in (the last chunk of a C_in that is
+//     no multiple of 32: 196) are zeros.  One buffer (10 KB), two barriers per chunk;
+//   - fragments: B for pixel group o is the fragment of pixel 16 o + (l & 15); A is 16 bytes of the packed weights [C_out][Kp]
+//     (Kp = C_in rounded up to 32, the tail zero) at [channel l & 15][chunk * 32 + 8 (l >> 4)], read from L2 once per (wave,
+//     chunk) and used for the 8 pixel groups.  Both operands are zero in the tail of the last chunk, so a NaN or an infinity
+//     there cannot arise;
 //   - accumulation order of an output element, fixed: chunks ascending; inside an MFMA the hardware's order over its 32
 //     channels.  float32 throughout, no atomics: the same inputs give the same bits on every run;
-//   - epilogue: c = half(acc + float(bias)), ONE rounding, then
-//       BIAS     out = c or relu(c) (torch.relu on the bits' meaning: NaN stays, -0 -> +0)
+//   - epilogue: c = mf_round(acc, bias), then
+//       BIAS     out = mf_relu(c)
 //       CONTEXT  c is a = w(net) and is never stored.  p = h(h(sigmoid(a)) * net) per pixel, gru_gates.h's statements as
 //                gru.hip's context kernel evaluates them.  A lane adds its p over the tile's pixel groups ascending (pixels
 //                r, r + 16, ..), the 16 lanes of a row (one channel each row and register) fold on the DPP network (row_shr
@@ -36,24 +29,14 @@
 //   the split fills the chip with n * ceil(hw / 128) workgroups and costs one small launch.  The one-launch form was not
 //   built, so the choice rests on this count, not on a measurement against it.
 // Built with -ffp-contract=off (the gate statements).  Resources from the cross-compile: profiles/conv1x1_resources.txt.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "common.h"
+#include "conv_mfma.h"
 #include "gru_gates.h"
 
 namespace dba {
 
-typedef _Float16 half_t;
-typedef half_t half8 __attribute__((ext_vector_type(8)));
-typedef float float4v __attribute__((ext_vector_type(4)));
-
 constexpr int PW_P = 128;                 // pixels of a workgroup's tile
 constexpr int PW_G = PW_P / 16;           // pixel groups of 16: N of one MFMA
-constexpr int PW_KC = 32;                 // channels per chunk: K of one MFMA
-constexpr int PW_XS = PW_KC + 8;          // LDS row pitch in halves (80 bytes)
-constexpr int PW_THREADS = 256;
-constexpr int PW_STAGE = PW_P * (PW_KC / 8) / PW_THREADS;   // (pixel, 8 channels) items per thread: 2
+constexpr int PW_STAGE = PW_P * (MF_KC / 8) / MF_THREADS;   // (pixel, 8 channels) items per thread: 2
 constexpr int PW_CMAX = 1024;             // the context tail keeps glo of one image in LDS
 
 enum { PW_BIAS = 0, PW_CONTEXT = 1 };
@@ -68,36 +51,34 @@ struct PwArgs {
 };
 
 template <int MT, int EPI>
-__global__ __launch_bounds__(PW_THREADS) void conv1x1_kernel(const PwArgs a) {
-  __shared__ __attribute__((aligned(16))) half_t xs[PW_P * PW_XS];
-  const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
-  const int r = lane & 15, q = lane >> 4;
+__global__ __launch_bounds__(MF_THREADS) void conv1x1_kernel(const PwArgs a) {
+  __shared__ __attribute__((aligned(16))) half_t xs[PW_P * MF_XS];
+  const MfWave wv;
+  const int r = wv.r, q = wv.q;
   const int img = blockIdx.x / a.tiles, tile = blockIdx.x - img * a.tiles;
   const int p0 = tile * PW_P;
-  const int co0 = blockIdx.y * (64 * MT) + g * (16 * MT);   // this wave's first output channel
+  const int co0 = wv.co0(MT);
 
   // where this thread's staging items lie: fixed over the chunks
   int s_lds[PW_STAGE], s_cg[PW_STAGE], s_off[PW_STAGE];   // LDS half index; first channel inside the chunk; plane offset, -1: zero
 #pragma unroll
   for (int k = 0; k < PW_STAGE; ++k) {
-    const int it = threadIdx.x + k * PW_THREADS;
+    const int it = threadIdx.x + k * MF_THREADS;
     const int cg = it / PW_P, p = it - cg * PW_P;
-    s_lds[k] = p * PW_XS + cg * 8;
+    s_lds[k] = p * MF_XS + cg * 8;
     s_cg[k] = cg * 8;
     s_off[k] = p0 + p < a.hw ? p0 + p : -1;
   }
 
   float4v acc[PW_G][MT];
 #pragma unroll
-  for (int o = 0; o < PW_G; ++o)
-#pragma unroll
-    for (int m = 0; m < MT; ++m) acc[o][m] = float4v{0.f, 0.f, 0.f, 0.f};
+  for (int o = 0; o < PW_G; ++o) mf_zero(acc[o]);
 
   const half_t *wrow = a.w + (size_t)(co0 + r) * a.kp + q * 8;   // + m * 16 * kp + chunk * 32
   const half_t *image = a.x + (size_t)img * a.c_in * a.hw;
 
 #pragma unroll 1
-  for (int ch0 = 0; ch0 < a.c_in; ch0 += PW_KC) {
+  for (int ch0 = 0; ch0 < a.c_in; ch0 += MF_KC) {
     half8 v[PW_STAGE];
 #pragma unroll
     for (int k = 0; k < PW_STAGE; ++k) {
@@ -116,7 +97,7 @@ __global__ __launch_bounds__(PW_THREADS) void conv1x1_kernel(const PwArgs a) {
     __syncthreads();
 #pragma unroll
     for (int o = 0; o < PW_G; ++o) {
-      const half8 xb = *reinterpret_cast<const half8 *>(&xs[(o * 16 + r) * PW_XS + q * 8]);
+      const half8 xb = mf_fragment(xs, o * 16 + r, q);
 #pragma unroll
       for (int m = 0; m < MT; ++m) acc[o][m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wa[m], xb, acc[o][m], 0, 0, 0);
     }
@@ -127,7 +108,7 @@ __global__ __launch_bounds__(PW_THREADS) void conv1x1_kernel(const PwArgs a) {
 #pragma unroll
   for (int m = 0; m < MT; ++m)
 #pragma unroll
-    for (int i = 0; i < 4; ++i) bf[m][i] = a.bias ? (float)a.bias[co0 + m * 16 + 4 * q + i] : 0.f;
+    for (int i = 0; i < 4; ++i) bf[m][i] = mf_bias(a.bias, co0 + m * 16 + 4 * q + i);
 
   if (EPI == PW_BIAS) {
 #pragma unroll
@@ -139,9 +120,7 @@ __global__ __launch_bounds__(PW_THREADS) void conv1x1_kernel(const PwArgs a) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int co = co0 + m * 16 + 4 * q + i;
-          const half_t c = (half_t)(acc[o][m][i] + bf[m][i]);
-          const float cf = (float)c;
-          a.out[((size_t)img * a.c_out + co) * a.hw + pix] = (a.relu && cf <= 0.f) ? (half_t)0.f : c;
+          a.out[((size_t)img * a.c_out + co) * a.hw + pix] = mf_relu(mf_round(acc[o][m][i], bf[m][i]), a.relu);
         }
     }
   } else {
@@ -159,7 +138,7 @@ __global__ __launch_bounds__(PW_THREADS) void conv1x1_kernel(const PwArgs a) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int co = co0 + m * 16 + 4 * q + i;   // c_out == c_in: the state's own channel
-          const float av = (float)(half_t)(acc[o][m][i] + bf[m][i]);
+          const float av = (float)mf_round(acc[o][m][i], bf[m][i]);
           const float nn = (float)image[(size_t)co * a.hw + pix];
           s[m][i] += rnd<half_t>(rnd<half_t>(sigmoid_f32(av)) * nn);
         }
@@ -180,14 +159,14 @@ __global__ __launch_bounds__(PW_THREADS) void conv1x1_kernel(const PwArgs a) {
 }
 
 // partial [n, tiles, c] -> glo [n, c]; wg [3c][c], bg [3c] or null -> gz, gr, gq [n, c]
-__global__ __launch_bounds__(PW_THREADS) void conv1x1_context_tail_kernel(const float *__restrict__ partial, int tiles, int c,
+__global__ __launch_bounds__(MF_THREADS) void conv1x1_context_tail_kernel(const float *__restrict__ partial, int tiles, int c,
                                                                           float inv_hw, const half_t *__restrict__ wg,
                                                                           const half_t *__restrict__ bg, half_t *__restrict__ glo,
                                                                           half_t *__restrict__ gz, half_t *__restrict__ gr,
                                                                           half_t *__restrict__ gq) {
   __shared__ float gs[PW_CMAX];
   const int img = blockIdx.x;
-  for (int ch = threadIdx.x; ch < c; ch += PW_THREADS) {
+  for (int ch = threadIdx.x; ch < c; ch += MF_THREADS) {
     const float *p = partial + (size_t)img * tiles * c + ch;
     float s = 0.0f;
     for (int t = 0; t < tiles; ++t) s += p[(size_t)t * c];
@@ -196,7 +175,7 @@ __global__ __launch_bounds__(PW_THREADS) void conv1x1_context_tail_kernel(const 
     gs[ch] = (float)h;
   }
   __syncthreads();
-  for (int o = threadIdx.x; o < 3 * c; o += PW_THREADS) {
+  for (int o = threadIdx.x; o < 3 * c; o += MF_THREADS) {
     const half8 *row = reinterpret_cast<const half8 *>(wg + (size_t)o * c);
     float acc = 0.0f;
     for (int k = 0; k < c / 8; ++k) {
@@ -217,11 +196,6 @@ using namespace dba;
 
 namespace {
 
-bool pw_overlaps(const void *p, size_t bytes, const void *q, size_t qbytes) {
-  const uintptr_t x = (uintptr_t)p, y = (uintptr_t)q;
-  return p && q && x < y + qbytes && y < x + bytes;
-}
-
 // the checks the two entry points share; fills the input half of the arguments
 int pw_input(PwArgs &a, const void *x, int c_in, const void *w, const void *bias, int c_out, int n, int hw) {
   if (n <= 0 || hw <= 0 || c_in <= 0 || c_out <= 0 || c_out % 64) return DBA_ERR_ARG;
@@ -232,7 +206,7 @@ int pw_input(PwArgs &a, const void *x, int c_in, const void *w, const void *bias
   const long long cmax = c_in > c_out ? c_in : c_out;
   if ((long long)hw * cmax > (long long)INT32_MAX) return DBA_ERR_ARG;   // an image's planes: int offsets
   const long long tiles = ((long long)hw + PW_P - 1) / PW_P;
-  if (tiles * n > (long long)INT32_MAX || c_out / 64 > 65535) return DBA_ERR_ARG;
+  if (!mf_grid_ok(tiles, n, c_out)) return DBA_ERR_ARG;
   a.x = (const half_t *)x;
   a.w = (const half_t *)w;
   a.bias = (const half_t *)bias;
@@ -247,20 +221,8 @@ int pw_input(PwArgs &a, const void *x, int c_in, const void *w, const void *bias
 
 // a written range must not share a byte with anything the launch reads
 bool pw_clobbers(const PwArgs &a, const void *dst, size_t bytes) {
-  return pw_overlaps(dst, bytes, a.x, (size_t)a.n * a.c_in * a.hw * 2) ||
-         pw_overlaps(dst, bytes, a.w, (size_t)a.c_out * a.kp * 2) || pw_overlaps(dst, bytes, a.bias, (size_t)a.c_out * 2);
-}
-
-template <int EPI>
-int pw_launch(const PwArgs &a, hipStream_t s) {
-  const bool wide = a.c_out % 128 == 0;
-  const dim3 grid((unsigned)(a.tiles * a.n), (unsigned)(a.c_out / (wide ? 128 : 64)));
-  if (wide)
-    hipLaunchKernelGGL((conv1x1_kernel<2, EPI>), grid, dim3(PW_THREADS), 0, s, a);
-  else
-    hipLaunchKernelGGL((conv1x1_kernel<1, EPI>), grid, dim3(PW_THREADS), 0, s, a);
-  DBA_LAUNCH_CHECK();
-  return DBA_OK;
+  return ranges_overlap(dst, bytes, a.x, (size_t)a.n * a.c_in * a.hw * 2) ||
+         ranges_overlap(dst, bytes, a.w, (size_t)a.c_out * a.kp * 2) || ranges_overlap(dst, bytes, a.bias, (size_t)a.c_out * 2);
 }
 
 }  // namespace
@@ -277,7 +239,7 @@ int dba_conv1x1_f16(const void *x, int c_in, const void *weight, const void *bia
   if (!out || ((uintptr_t)out & 1) || pw_clobbers(a, out, (size_t)n * c_out * hw * 2)) return DBA_ERR_ARG;
   a.out = (half_t *)out;
   a.relu = relu != 0;
-  return pw_launch<PW_BIAS>(a, (hipStream_t)stream);
+  return mf_launch<conv1x1_kernel<2, PW_BIAS>, conv1x1_kernel<1, PW_BIAS>>(a, (hipStream_t)stream);
 }
 
 size_t dba_conv1x1_context_workspace_bytes(int n, int c, int hw) {
@@ -299,19 +261,19 @@ int dba_conv1x1_context_f16(const void *net, const void *weight, const void *bia
   const size_t gbytes = (size_t)n * c * 2, wsbytes = dba_conv1x1_context_workspace_bytes(n, c, hw);
   for (int i = 0; i < 4; ++i) {
     void *o = outs[i];
-    if (!o || ((uintptr_t)o & 1) || pw_clobbers(a, o, gbytes) || pw_overlaps(o, gbytes, glo_weight, (size_t)3 * c * c * 2) ||
-        pw_overlaps(o, gbytes, glo_bias, (size_t)3 * c * 2) || pw_overlaps(o, gbytes, workspace, wsbytes))
+    if (!o || ((uintptr_t)o & 1) || pw_clobbers(a, o, gbytes) || ranges_overlap(o, gbytes, glo_weight, (size_t)3 * c * c * 2) ||
+        ranges_overlap(o, gbytes, glo_bias, (size_t)3 * c * 2) || ranges_overlap(o, gbytes, workspace, wsbytes))
       return DBA_ERR_ARG;
     for (int j = i + 1; j < 4; ++j)
-      if (pw_overlaps(o, gbytes, outs[j], gbytes)) return DBA_ERR_ARG;
+      if (ranges_overlap(o, gbytes, outs[j], gbytes)) return DBA_ERR_ARG;
   }
-  if (pw_clobbers(a, workspace, wsbytes) || pw_overlaps(workspace, wsbytes, glo_weight, (size_t)3 * c * c * 2) ||
-      pw_overlaps(workspace, wsbytes, glo_bias, (size_t)3 * c * 2))
+  if (pw_clobbers(a, workspace, wsbytes) || ranges_overlap(workspace, wsbytes, glo_weight, (size_t)3 * c * c * 2) ||
+      ranges_overlap(workspace, wsbytes, glo_bias, (size_t)3 * c * 2))
     return DBA_ERR_ARG;
   a.partial = (float *)workspace;
-  const int rl = pw_launch<PW_CONTEXT>(a, (hipStream_t)stream);
+  const int rl = mf_launch<conv1x1_kernel<2, PW_CONTEXT>, conv1x1_kernel<1, PW_CONTEXT>>(a, (hipStream_t)stream);
   if (rl != DBA_OK) return rl;
-  hipLaunchKernelGGL(conv1x1_context_tail_kernel, dim3((unsigned)n), dim3(PW_THREADS), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(conv1x1_context_tail_kernel, dim3((unsigned)n), dim3(MF_THREADS), 0, (hipStream_t)stream,
                      (const float *)workspace, a.tiles, c, 1.0f / (float)hw, (const half_t *)glo_weight, (const half_t *)glo_bias,
                      (half_t *)glo, (half_t *)gz, (half_t *)gr, (half_t *)gq);
   DBA_LAUNCH_CHECK();

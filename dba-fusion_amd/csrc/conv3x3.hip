@@ -5,56 +5,38 @@
 //   dba_conv3x3_gates_f16  <- z = sigmoid(convz(x) + gz); r = sigmoid(convr(x) + gr); r * net       (dbaf/modules/gru.py:27-29)
 //   dba_conv3x3_blend_f16  <- q = tanh(convq(cat([r*net, inp])) + gq); (1 - z) * net + z * q          (gru.py:29-31)
 //
-// conv3x3_kernel<MT, EPI>.  Implicit GEMM on mfma_f32_16x16x32_f16: M = output channels (A = the packed weights), N = 16
-// consecutive pixels of a map row (B = the staged input), K = 32 input channels of one tap.
-//   - tile: one workgroup (4 waves) owns 16 x 16 output pixels of one image and 64 * MT output channels (MT = 2 when C_out is
-//     a multiple of 128, else 1); wave g owns the channels g * 16 * MT .. + 16 * MT of that block for all 256 pixels:
-//     16 x MT accumulator tiles of 4 floats (128 registers at MT = 2).  blockIdx.x = image * tiles + tile, blockIdx.y = the
-//     channel block;
-//   - staging: the input is walked in chunks of 32 channels (c0 and c1 are multiples of 32, so a chunk lies in ONE of the two
-//     sources).  The workgroup stages the chunk's 18 x 18 pixels (the tile and its one-pixel halo) once, transposed, into
-//     LDS rows of 32 + 8 halves (80-byte pitch): a thread takes one halo pixel and 8 channels (8 guarded 2-byte loads,
-//     neighbouring threads neighbouring pixels) and writes one 16-byte LDS vector.  Positions outside the image are
-//     written as zeros and never dereferenced: the map's borders, the tail of a row and the tail of the last image.
-//     One buffer, two barriers per chunk, no double buffering: the kernel is held to two waves per SIMD
-//     (amdgpu_waves_per_eu(2, 2): 243 VGPRs at MT = 2, no scratch), so two workgroups share a CU (26 KB of LDS each) and
-//     one stages while the other multiplies.  The 80-byte pitch leaves two-way conflicts inside a ds_read_b128 lane group;
-//   - fragments: B for output row o, tap (ky, kx) is the LDS read of halo row o + ky at pixel offset kx: lane l reads the 16
-//     bytes [pixel (l & 15) + kx][channels 8 (l >> 4) ..], one aligned ds_read_b128.  A halo row's fragment at a given kx is
-//     read ONCE and feeds the three taps ky (output rows ir, ir - 1, ir - 2): 54 LDS reads per chunk and wave for up to
-//     144 * MT MFMAs.  A for tap t is 16 bytes of the packed weights [9][C_out][C_in] at [t][channel l & 15][chunk * 32 +
-//     8 (l >> 4)], read from L2 once per (workgroup, chunk, tap) and used for 16 pixel groups;
+// conv3x3_kernel<MT, EPI>: conv_mfma.h's GEMM with N = 16 consecutive pixels of a map row and K = 32 input channels of one tap.
+//   - tile: 16 x 16 output pixels; a wave holds 16 x MT accumulator tiles of 4 floats (128 registers at MT = 2);
+//   - staging: c0 and c1 are multiples of 32, so a chunk lies in ONE of the two sources.  The workgroup stages the chunk's
+//     18 x 18 pixels (the tile and its one-pixel halo) once.  Positions outside the image are zeros: the map's borders, the
+//     tail of a row and the tail of the last image.  One buffer, two barriers per chunk, no double buffering: the kernel is
+//     held to two waves per SIMD (amdgpu_waves_per_eu(2, 2): 243 VGPRs at MT = 2, no scratch), so two workgroups share a CU
+//     (26 KB of LDS each) and one stages while the other multiplies;
+//   - fragments: B for output row o, tap (ky, kx) is the fragment of halo row o + ky at pixel offset kx.  A halo row's
+//     fragment at a given kx is read ONCE and feeds the three taps ky (output rows ir, ir - 1, ir - 2): 54 LDS reads per chunk
+//     and wave for up to 144 * MT MFMAs.  A for tap t is 16 bytes of the packed weights [9][C_out][C_in] at [t][channel l & 15]
+//     [chunk * 32 + 8 (l >> 4)], read from L2 once per (workgroup, chunk, tap) and used for 16 pixel groups;
 //   - accumulation order of an output element, fixed: chunks ascending; inside a chunk kx = 0, 1, 2; inside kx the halo rows
 //     ascending (ky = 0, 1, 2); inside an MFMA the hardware's order over its 32 channels.  float32 throughout, no atomics:
 //     the same inputs give the same bits on every run;
-//   - epilogue: c = half(acc + float(bias)), ONE rounding (what a stock half convolution stores), then per variant
-//       BIAS   out = c or relu(c) (torch.relu on the bits: NaN stays, -0 -> +0)
+//   - epilogue: c = mf_round(acc, bias), then per variant
+//       BIAS   out = mf_relu(c)
 //       PAIR   BIAS with C_out = 2c written as two tensors [n, c, h, w]: channels < c -> out, channels >= c -> out2
 //       GATES  channels < c: z = gru_gate(c, gz) -> z_out; channels >= c: gru_reset_value(c, gr, net) -> rnet_out
 //       BLEND  out = gru_blend_value(z, c, gq, net); out may be net (a lane reads its own element before it writes it)
 //     with the statements of gru_gates.h, the ones gru.hip's kernels evaluate.  A lane holds 4 consecutive channels of one
 //     pixel; a store instruction writes 4 channel planes x 16 consecutive pixels.
 // Built with -ffp-contract=off (the gate statements).  Resources from the cross-compile: profiles/conv3x3_resources.txt.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "common.h"
+#include "conv_mfma.h"
 #include "gru_gates.h"
 
 namespace dba {
 
-typedef _Float16 half_t;
-typedef half_t half8 __attribute__((ext_vector_type(8)));
-typedef float float4v __attribute__((ext_vector_type(4)));
-
 constexpr int CV_T = 16;                  // the tile's rows and columns
 constexpr int CV_H = CV_T + 2;            // with the halo
 constexpr int CV_HP = CV_H * CV_H;        // halo pixels: 324
-constexpr int CV_KC = 32;                 // channels per chunk: K of one MFMA
-constexpr int CV_XS = CV_KC + 8;          // LDS row pitch in halves (80 bytes)
-constexpr int CV_THREADS = 256;
-constexpr int CV_ITEMS = CV_HP * (CV_KC / 8);                            // (pixel, 8 channels) items of a chunk
-constexpr int CV_STAGE = (CV_ITEMS + CV_THREADS - 1) / CV_THREADS;       // per thread: 6
+constexpr int CV_ITEMS = CV_HP * (MF_KC / 8);                            // (pixel, 8 channels) items of a chunk
+constexpr int CV_STAGE = (CV_ITEMS + MF_THREADS - 1) / MF_THREADS;       // per thread: 6
 
 enum { CV_BIAS = 0, CV_GATES = 1, CV_BLEND = 2, CV_PAIR = 3 };
 
@@ -70,40 +52,38 @@ struct ConvArgs {
 };
 
 template <int MT, int EPI>
-__global__ __launch_bounds__(CV_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv3x3_kernel(const ConvArgs a) {
-  __shared__ __attribute__((aligned(16))) half_t xs[CV_HP * CV_XS];
-  const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
-  const int r = lane & 15, q = lane >> 4;
+__global__ __launch_bounds__(MF_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv3x3_kernel(const ConvArgs a) {
+  __shared__ __attribute__((aligned(16))) half_t xs[CV_HP * MF_XS];
+  const MfWave wv;
+  const int r = wv.r, q = wv.q;
   const int img = blockIdx.x / a.tiles, tile = blockIdx.x - img * a.tiles;
   const int ty0 = (tile / a.tiles_x) * CV_T, tx0 = (tile - (tile / a.tiles_x) * a.tiles_x) * CV_T;
   const int HW = a.h * a.wd, c_in = a.c0 + a.c1;
-  const int co0 = blockIdx.y * (64 * MT) + g * (16 * MT);   // this wave's first output channel
+  const int co0 = wv.co0(MT);
   const int rows = min(CV_T, a.h - ty0);                    // output rows of the tile inside the image (uniform)
 
   // where this thread's staging items lie: fixed over the chunks
   int s_lds[CV_STAGE], s_off[CV_STAGE];   // LDS half index; offset inside the chunk's planes, -1: zero
 #pragma unroll
   for (int k = 0; k < CV_STAGE; ++k) {
-    const int it = threadIdx.x + k * CV_THREADS;
+    const int it = threadIdx.x + k * MF_THREADS;
     const int cg = it / CV_HP, p = it - cg * CV_HP;
     const int iy = p / CV_H, ix = p - iy * CV_H;
     const int gy = ty0 - 1 + iy, gx = tx0 - 1 + ix;
     const bool ok = it < CV_ITEMS && gy >= 0 && gy < a.h && gx >= 0 && gx < a.wd;
-    s_lds[k] = it < CV_ITEMS ? p * CV_XS + cg * 8 : -1;
+    s_lds[k] = it < CV_ITEMS ? p * MF_XS + cg * 8 : -1;
     s_off[k] = ok ? cg * 8 * HW + gy * a.wd + gx : -1;
   }
 
   float4v acc[CV_T][MT];
 #pragma unroll
-  for (int o = 0; o < CV_T; ++o)
-#pragma unroll
-    for (int m = 0; m < MT; ++m) acc[o][m] = float4v{0.f, 0.f, 0.f, 0.f};
+  for (int o = 0; o < CV_T; ++o) mf_zero(acc[o]);
 
   const half_t *wrow = a.w + (size_t)(co0 + r) * c_in + q * 8;   // + (tap * c_out + m * 16) * c_in + chunk * 32
   const size_t tap_stride = (size_t)a.c_out * c_in;
 
 #pragma unroll 1
-  for (int ch0 = 0; ch0 < c_in; ch0 += CV_KC) {
+  for (int ch0 = 0; ch0 < c_in; ch0 += MF_KC) {
     const half_t *planes = ch0 < a.c0 ? a.src0 + ((size_t)img * a.c0 + ch0) * HW
                                       : a.src1 + ((size_t)img * a.c1_total + a.src1_first + (ch0 - a.c0)) * HW;
     half8 v[CV_STAGE];
@@ -129,7 +109,7 @@ __global__ __launch_bounds__(CV_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
 #pragma unroll
       for (int ir = 0; ir < CV_H; ++ir) {
         if (ir >= rows + 2) continue;   // uniform: halo rows that only feed output rows outside the image
-        const half8 xb = *reinterpret_cast<const half8 *>(&xs[(ir * CV_H + kx + r) * CV_XS + q * 8]);
+        const half8 xb = mf_fragment(xs, ir * CV_H + kx + r, q);
 #pragma unroll
         for (int ky = 0; ky < 3; ++ky) {
           const int o = ir - ky;
@@ -150,7 +130,7 @@ __global__ __launch_bounds__(CV_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int co = co0 + m * 16 + 4 * q + i;
-      bf[m][i] = a.bias ? (float)a.bias[co] : 0.f;
+      bf[m][i] = mf_bias(a.bias, co);
       if (EPI == CV_GATES)
         gt[m][i] = co < a.c ? (float)a.g0[(size_t)img * a.c + co] : (float)a.g1[(size_t)img * a.c + (co - a.c)];
       else if (EPI == CV_BLEND)
@@ -167,14 +147,12 @@ __global__ __launch_bounds__(CV_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int co = co0 + m * 16 + 4 * q + i;
-        const half_t c = (half_t)(acc[o][m][i] + bf[m][i]);
+        const half_t c = mf_round(acc[o][m][i], bf[m][i]);
         if (EPI == CV_BIAS) {
-          const float cf = (float)c;
-          a.out[((size_t)img * a.c_out + co) * HW + pix] = (a.relu && cf <= 0.f) ? (half_t)0.f : c;
+          a.out[((size_t)img * a.c_out + co) * HW + pix] = mf_relu(c, a.relu);
         } else if (EPI == CV_PAIR) {
-          const float cf = (float)c;
           half_t *dst = co < a.c ? a.out + ((size_t)img * a.c + co) * HW : a.out2 + ((size_t)img * a.c + (co - a.c)) * HW;
-          dst[pix] = (a.relu && cf <= 0.f) ? (half_t)0.f : c;
+          dst[pix] = mf_relu(c, a.relu);
         } else if (EPI == CV_GATES) {
           if (co < a.c) {
             a.out[((size_t)img * a.c + co) * HW + pix] = (half_t)gru_gate<half_t>((float)c, gt[m][i]);
@@ -197,11 +175,6 @@ using namespace dba;
 
 namespace {
 
-bool cv_overlaps(const void *p, size_t bytes, const void *q, size_t qbytes) {
-  const uintptr_t x = (uintptr_t)p, y = (uintptr_t)q;
-  return p && q && x < y + qbytes && y < x + bytes;
-}
-
 // the checks the three entry points share; fills the input half of the arguments
 int cv_input(ConvArgs &a, const void *src0, int c0, const void *src1, int c1, int c1_total, int src1_first, const void *w,
              const void *bias, int c_out, int n, int h, int wd) {
@@ -215,7 +188,7 @@ int cv_input(ConvArgs &a, const void *src0, int c0, const void *src1, int c1, in
   const long long cmax = (long long)c0 + c1 > c_out ? (long long)c0 + c1 : c_out;
   if (hw * (cmax > c1_total ? cmax : c1_total) > (long long)INT32_MAX) return DBA_ERR_ARG;   // an image's planes: int offsets
   const long long tiles_x = (wd + CV_T - 1) / CV_T, tiles = tiles_x * ((h + CV_T - 1) / CV_T);
-  if (tiles * n > (long long)INT32_MAX) return DBA_ERR_ARG;
+  if (!mf_grid_ok(tiles, n, c_out)) return DBA_ERR_ARG;
   a.src0 = (const half_t *)src0;
   a.src1 = (const half_t *)(c1 > 0 ? src1 : src0);
   a.c0 = c0;
@@ -236,22 +209,10 @@ int cv_input(ConvArgs &a, const void *src0, int c0, const void *src1, int c1, in
 // a written tensor [n, c, h, w] must not share a byte with anything the launch reads through the halo
 bool cv_clobbers(const ConvArgs &a, const void *dst, int c) {
   const size_t hw = (size_t)a.h * a.wd, bytes = (size_t)a.n * c * hw * 2;
-  return cv_overlaps(dst, bytes, a.src0, (size_t)a.n * a.c0 * hw * 2) ||
-         (a.c1 > 0 && cv_overlaps(dst, bytes, a.src1, (size_t)a.n * a.c1_total * hw * 2)) ||
-         cv_overlaps(dst, bytes, a.w, (size_t)9 * a.c_out * (a.c0 + a.c1) * 2) ||
-         cv_overlaps(dst, bytes, a.bias, (size_t)a.c_out * 2);
-}
-
-template <int EPI>
-int cv_launch(const ConvArgs &a, hipStream_t s) {
-  const bool wide = a.c_out % 128 == 0;
-  const dim3 grid((unsigned)(a.tiles * a.n), (unsigned)(a.c_out / (wide ? 128 : 64)));
-  if (wide)
-    hipLaunchKernelGGL((conv3x3_kernel<2, EPI>), grid, dim3(CV_THREADS), 0, s, a);
-  else
-    hipLaunchKernelGGL((conv3x3_kernel<1, EPI>), grid, dim3(CV_THREADS), 0, s, a);
-  DBA_LAUNCH_CHECK();
-  return DBA_OK;
+  return ranges_overlap(dst, bytes, a.src0, (size_t)a.n * a.c0 * hw * 2) ||
+         (a.c1 > 0 && ranges_overlap(dst, bytes, a.src1, (size_t)a.n * a.c1_total * hw * 2)) ||
+         ranges_overlap(dst, bytes, a.w, (size_t)9 * a.c_out * (a.c0 + a.c1) * 2) ||
+         ranges_overlap(dst, bytes, a.bias, (size_t)a.c_out * 2);
 }
 
 }  // namespace
@@ -268,7 +229,7 @@ int dba_conv3x3_f16(const void *src0, int c0, const void *src1, int c1, int c1_t
   if (!out || ((uintptr_t)out & 1) || cv_clobbers(a, out, c_out)) return DBA_ERR_ARG;
   a.out = (half_t *)out;
   a.relu = relu != 0;
-  return cv_launch<CV_BIAS>(a, (hipStream_t)stream);
+  return mf_launch<conv3x3_kernel<2, CV_BIAS>, conv3x3_kernel<1, CV_BIAS>>(a, (hipStream_t)stream);
 }
 
 int dba_conv3x3_pair_f16(const void *src0, int c0, const void *src1, int c1, int c1_total, int src1_first, const void *weight,
@@ -279,12 +240,12 @@ int dba_conv3x3_pair_f16(const void *src0, int c0, const void *src1, int c1, int
   if (rc != DBA_OK) return rc;
   if (!out0 || !out1 || (((uintptr_t)out0 | (uintptr_t)out1) & 1)) return DBA_ERR_ARG;
   const size_t bytes = (size_t)n * c * h * w * 2;
-  if (cv_clobbers(a, out0, c) || cv_clobbers(a, out1, c) || cv_overlaps(out0, bytes, out1, bytes)) return DBA_ERR_ARG;
+  if (cv_clobbers(a, out0, c) || cv_clobbers(a, out1, c) || ranges_overlap(out0, bytes, out1, bytes)) return DBA_ERR_ARG;
   a.out = (half_t *)out0;
   a.out2 = (half_t *)out1;
   a.c = c;
   a.relu = relu != 0;
-  return cv_launch<CV_PAIR>(a, (hipStream_t)stream);
+  return mf_launch<conv3x3_kernel<2, CV_PAIR>, conv3x3_kernel<1, CV_PAIR>>(a, (hipStream_t)stream);
 }
 
 int dba_conv3x3_gates_f16(const void *src0, int c0, const void *src1, int c1, int c1_total, int src1_first,
@@ -299,17 +260,17 @@ int dba_conv3x3_gates_f16(const void *src0, int c0, const void *src1, int c1, in
   const size_t bytes = (size_t)n * c * h * w * 2, gbytes = (size_t)n * c * 2;
   void *const outs[2] = {z_out, rnet_out};
   for (void *o : outs)
-    if (cv_clobbers(a, o, c) || cv_overlaps(o, bytes, gz, gbytes) || cv_overlaps(o, bytes, gr, gbytes) ||
-        cv_overlaps(o, bytes, net, bytes))
+    if (cv_clobbers(a, o, c) || ranges_overlap(o, bytes, gz, gbytes) || ranges_overlap(o, bytes, gr, gbytes) ||
+        ranges_overlap(o, bytes, net, bytes))
       return DBA_ERR_ARG;
-  if (cv_overlaps(z_out, bytes, rnet_out, bytes)) return DBA_ERR_ARG;
+  if (ranges_overlap(z_out, bytes, rnet_out, bytes)) return DBA_ERR_ARG;
   a.out = (half_t *)z_out;
   a.out2 = (half_t *)rnet_out;
   a.g0 = (const half_t *)gz;
   a.g1 = (const half_t *)gr;
   a.net = (const half_t *)net;
   a.c = c;
-  return cv_launch<CV_GATES>(a, (hipStream_t)stream);
+  return mf_launch<conv3x3_kernel<2, CV_GATES>, conv3x3_kernel<1, CV_GATES>>(a, (hipStream_t)stream);
 }
 
 int dba_conv3x3_blend_f16(const void *src0, int c0, const void *src1, int c1, int c1_total, int src1_first,
@@ -321,13 +282,13 @@ int dba_conv3x3_blend_f16(const void *src0, int c0, const void *src1, int c1, in
   if (!gq || !z || !net || !out) return DBA_ERR_ARG;
   if (((uintptr_t)gq | (uintptr_t)z | (uintptr_t)net | (uintptr_t)out) & 1) return DBA_ERR_ARG;
   const size_t bytes = (size_t)n * c * h * w * 2, gbytes = (size_t)n * c * 2;
-  if (cv_clobbers(a, out, c) || cv_overlaps(out, bytes, gq, gbytes) || cv_overlaps(out, bytes, z, bytes)) return DBA_ERR_ARG;
-  if (out != net && cv_overlaps(out, bytes, net, bytes)) return DBA_ERR_ARG;
+  if (cv_clobbers(a, out, c) || ranges_overlap(out, bytes, gq, gbytes) || ranges_overlap(out, bytes, z, bytes)) return DBA_ERR_ARG;
+  if (out != net && ranges_overlap(out, bytes, net, bytes)) return DBA_ERR_ARG;
   a.out = (half_t *)out;
   a.g0 = (const half_t *)gq;
   a.z = (const half_t *)z;
   a.net = (const half_t *)net;
-  return cv_launch<CV_BLEND>(a, (hipStream_t)stream);
+  return mf_launch<conv3x3_kernel<2, CV_BLEND>, conv3x3_kernel<1, CV_BLEND>>(a, (hipStream_t)stream);
 }
 
 }  // extern "C"

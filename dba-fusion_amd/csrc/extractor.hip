@@ -280,11 +280,6 @@ using namespace dba;
 
 namespace {
 
-bool overlaps(const void *p, long long bytes, const void *q, long long qbytes) {
-  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-  return a < b + (uintptr_t)qbytes && b < a + (uintptr_t)bytes;
-}
-
 bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
 int item_size(int dtype) { return dtype == DBA_F16 ? 2 : dtype == DBA_F32 ? 4 : 0; }
@@ -460,8 +455,8 @@ int dba_enc_norm(const void *x, int planes, int hw, float eps, int relu, int dty
   if (!x || !out || !plane_extents_ok(planes, hw) || !(eps >= 0.0f)) return DBA_ERR_ARG;
   if (((uintptr_t)x | (uintptr_t)out) % isz || (stats && (uintptr_t)stats % 4)) return DBA_ERR_ARG;
   const long long bytes = (long long)planes * hw * isz, sbytes = (long long)planes * 8;
-  if (out != x && overlaps(out, bytes, x, bytes)) return DBA_ERR_ARG;
-  if (stats && (overlaps(stats, sbytes, x, bytes) || overlaps(stats, sbytes, out, bytes))) return DBA_ERR_ARG;
+  if (out != x && ranges_overlap(out, bytes, x, bytes)) return DBA_ERR_ARG;
+  if (stats && (ranges_overlap(stats, sbytes, x, bytes) || ranges_overlap(stats, sbytes, out, bytes))) return DBA_ERR_ARG;
   return dtype == DBA_F16 ? launch_norm<_Float16>(x, out, stats, planes, hw, eps, relu != 0, (hipStream_t)stream)
                           : launch_norm<float>(x, out, stats, planes, hw, eps, relu != 0, (hipStream_t)stream);
 }
@@ -476,12 +471,12 @@ int dba_enc_norm_skip(const void *x, const void *skip, const void *d, int planes
   if ((stats && (uintptr_t)stats % 4) || (stats_d && (uintptr_t)stats_d % 4)) return DBA_ERR_ARG;
   if (stats_d && !d) return DBA_ERR_ARG;
   const long long bytes = (long long)planes * hw * isz, sbytes = (long long)planes * 8;
-  if (out != x && overlaps(out, bytes, x, bytes)) return DBA_ERR_ARG;
-  if (overlaps(out, bytes, side, bytes)) return DBA_ERR_ARG;
+  if (out != x && ranges_overlap(out, bytes, x, bytes)) return DBA_ERR_ARG;
+  if (ranges_overlap(out, bytes, side, bytes)) return DBA_ERR_ARG;
   for (float *st : {stats, stats_d})
-    if (st && (overlaps(st, sbytes, x, bytes) || overlaps(st, sbytes, out, bytes) || overlaps(st, sbytes, side, bytes)))
+    if (st && (ranges_overlap(st, sbytes, x, bytes) || ranges_overlap(st, sbytes, out, bytes) || ranges_overlap(st, sbytes, side, bytes)))
       return DBA_ERR_ARG;
-  if (stats && stats_d && overlaps(stats, sbytes, stats_d, sbytes)) return DBA_ERR_ARG;
+  if (stats && stats_d && ranges_overlap(stats, sbytes, stats_d, sbytes)) return DBA_ERR_ARG;
   return dtype == DBA_F16
              ? launch_skip<_Float16>(x, side, d != nullptr, out, stats, stats_d, planes, hw, eps, (hipStream_t)stream)
              : launch_skip<float>(x, side, d != nullptr, out, stats, stats_d, planes, hw, eps, (hipStream_t)stream);
@@ -493,8 +488,8 @@ int dba_enc_relu_skip(const void *x, const void *skip, long long count, int dtyp
   if (!x || !skip || !out || count <= 0 || grid_beyond(1, count, ENC_UNROLL * (16 / isz))) return DBA_ERR_ARG;
   if (((uintptr_t)x | (uintptr_t)skip | (uintptr_t)out) % isz) return DBA_ERR_ARG;
   const long long bytes = count * isz;
-  if (out != x && overlaps(out, bytes, x, bytes)) return DBA_ERR_ARG;
-  if (overlaps(out, bytes, skip, bytes)) return DBA_ERR_ARG;
+  if (out != x && ranges_overlap(out, bytes, x, bytes)) return DBA_ERR_ARG;
+  if (ranges_overlap(out, bytes, skip, bytes)) return DBA_ERR_ARG;
   return dtype == DBA_F16 ? launch_relu_skip<_Float16>(x, skip, out, count, (hipStream_t)stream)
                           : launch_relu_skip<float>(x, skip, out, count, (hipStream_t)stream);
 }
@@ -507,7 +502,7 @@ int dba_enc_image(const void *img, int n, int H, int W, int src_dtype, int dtype
   if ((uintptr_t)img % ssz || (uintptr_t)out % isz) return DBA_ERR_ARG;
   const int hw = H * W;
   if (grid_beyond(3LL * n, hw, 4)) return DBA_ERR_ARG;
-  if (overlaps(out, 3LL * n * hw * isz, img, 3LL * n * hw * ssz)) return DBA_ERR_ARG;
+  if (ranges_overlap(out, 3LL * n * hw * isz, img, 3LL * n * hw * ssz)) return DBA_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
   if (src_dtype == DBA_U8)
     return dtype == DBA_F16 ? launch_image<uint8_t, _Float16>(img, out, n, hw, s) : launch_image<uint8_t, float>(img, out, n, hw, s);
@@ -523,7 +518,7 @@ int dba_enc_context_split(const void *x, int n, int c_net, int c_inp, int hw, in
   if (run_net + run_inp > (long long)INT32_MAX || grid_beyond(n, run_net + run_inp, ENC_UNROLL * (16 / isz))) return DBA_ERR_ARG;
   if (((uintptr_t)x | (uintptr_t)net | (uintptr_t)inp) % isz) return DBA_ERR_ARG;
   const long long nb = run_net * n * isz, ib = run_inp * n * isz;
-  if (overlaps(net, nb, x, nb + ib) || overlaps(inp, ib, x, nb + ib) || overlaps(net, nb, inp, ib)) return DBA_ERR_ARG;
+  if (ranges_overlap(net, nb, x, nb + ib) || ranges_overlap(inp, ib, x, nb + ib) || ranges_overlap(net, nb, inp, ib)) return DBA_ERR_ARG;
   return dtype == DBA_F16 ? launch_context_split<_Float16>(x, net, inp, n, run_net, run_inp, (hipStream_t)stream)
                           : launch_context_split<float>(x, net, inp, n, run_net, run_inp, (hipStream_t)stream);
 }

@@ -278,12 +278,6 @@ using namespace dba;
 
 namespace {
 
-// [p, p + bytes) and [q, q + qbytes) share a byte
-bool overlaps(const void *p, long long bytes, const void *q, long long qbytes) {
-  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-  return a < b + (uintptr_t)qbytes && b < a + (uintptr_t)bytes;
-}
-
 bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
 int item_size(int dtype) { return dtype == DBA_F16 ? 2 : dtype == DBA_F32 ? 4 : 0; }
@@ -377,7 +371,7 @@ static int pack_impl(const void *const *srcs, const int *channels, int n_src, in
     t.src[k] = (const char *)srcs[k];
     t.run[k] = (long long)channels[k] * hw * isz;
     t.off[k] = k ? t.off[k - 1] + t.run[k - 1] : 0;
-    if (overlaps(dst, t.row_bytes * n, srcs[k], t.run[k] * n)) return DBA_ERR_ARG;
+    if (ranges_overlap(dst, t.row_bytes * n, srcs[k], t.run[k] * n)) return DBA_ERR_ARG;
     bits |= (uintptr_t)srcs[k] | (uintptr_t)t.run[k];
   }
   t.width = (bits & 15) == 0 ? 16 : (bits & 7) == 0 ? 8 : (bits & 3) == 0 ? 4 : 2;  // every run starts and ends on it
@@ -416,7 +410,7 @@ int dba_gru_context(const void *a, const void *net, int n, int c, int hw, int dt
   if (!a || !net || !glo || !extents_ok(n, c, hw)) return DBA_ERR_ARG;
   if (((uintptr_t)a | (uintptr_t)net | (uintptr_t)glo) % isz) return DBA_ERR_ARG;
   const long long bytes = (long long)n * c * hw * isz, gbytes = (long long)n * c * isz;
-  if (overlaps(glo, gbytes, a, bytes) || overlaps(glo, gbytes, net, bytes)) return DBA_ERR_ARG;
+  if (ranges_overlap(glo, gbytes, a, bytes) || ranges_overlap(glo, gbytes, net, bytes)) return DBA_ERR_ARG;
   return dtype == DBA_F16 ? launch_context<_Float16>(a, net, glo, n * c, hw, (hipStream_t)stream)
                           : launch_context<float>(a, net, glo, n * c, hw, (hipStream_t)stream);
 }
@@ -429,7 +423,7 @@ int dba_gru_reset(void *buf, int c_total, const void *cr, const void *gr, const 
   if (((uintptr_t)buf | (uintptr_t)cr | (uintptr_t)gr | (uintptr_t)net) % isz) return DBA_ERR_ARG;
   const long long bytes = (long long)n * c * hw * isz, gbytes = (long long)n * c * isz;
   const long long bbytes = (long long)n * c_total * hw * isz;
-  if (overlaps(buf, bbytes, cr, bytes) || overlaps(buf, bbytes, gr, gbytes) || overlaps(buf, bbytes, net, bytes))
+  if (ranges_overlap(buf, bbytes, cr, bytes) || ranges_overlap(buf, bbytes, gr, gbytes) || ranges_overlap(buf, bbytes, net, bytes))
     return DBA_ERR_ARG;
   const long long stride = (long long)c_total * hw;
   return dtype == DBA_F16 ? launch_reset<_Float16>(buf, stride, cr, gr, net, n, c, hw, (hipStream_t)stream)
@@ -443,10 +437,10 @@ int dba_gru_blend(const void *cz, const void *gz, const void *cq, const void *gq
   if (!cz || !gz || !cq || !gq || !net || !out || !extents_ok(n, c, hw)) return DBA_ERR_ARG;
   if (((uintptr_t)cz | (uintptr_t)gz | (uintptr_t)cq | (uintptr_t)gq | (uintptr_t)net | (uintptr_t)out) % isz) return DBA_ERR_ARG;
   const long long bytes = (long long)n * c * hw * isz, gbytes = (long long)n * c * isz;
-  if (overlaps(out, bytes, cz, bytes) || overlaps(out, bytes, cq, bytes) || overlaps(out, bytes, gz, gbytes) ||
-      overlaps(out, bytes, gq, gbytes))
+  if (ranges_overlap(out, bytes, cz, bytes) || ranges_overlap(out, bytes, cq, bytes) || ranges_overlap(out, bytes, gz, gbytes) ||
+      ranges_overlap(out, bytes, gq, gbytes))
     return DBA_ERR_ARG;
-  if (out != net && overlaps(out, bytes, net, bytes)) return DBA_ERR_ARG;
+  if (out != net && ranges_overlap(out, bytes, net, bytes)) return DBA_ERR_ARG;
   return dtype == DBA_F16 ? launch_blend<_Float16>(cz, gz, cq, gq, net, out, n, c, hw, (hipStream_t)stream)
                           : launch_blend<float>(cz, gz, cq, gq, net, out, n, c, hw, (hipStream_t)stream);
 }

@@ -318,12 +318,6 @@ using namespace dba;
 
 namespace {
 
-bool overlaps(const void *p, long long bytes, const void *q, long long qbytes) {
-  if (!p || !q) return false;
-  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-  return a < b + (uintptr_t)qbytes && b < a + (uintptr_t)bytes;
-}
-
 template <typename T, int K>
 int launch_heads(const UpdHeads &hs, bool vec, int n, int c, int ht, int wd, unsigned tiles_x, unsigned tiles, unsigned grid,
                  hipStream_t s) {
@@ -373,17 +367,18 @@ int dba_upd_heads(const dba_upd_head_t *heads, int n_heads, int n, int c, int ht
   for (int i = 0; i < n_heads; i++) {
     const dba_upd_head_t &h = heads[i];
     const long long obytes = (long long)n * hw * h.k * isz, sbytes = (long long)n * hw * h.k * 4;
-    if (overlaps(h.out, obytes, h.sum, sbytes)) return DBA_ERR_ARG;
+    if (ranges_overlap(h.out, obytes, h.sum, sbytes)) return DBA_ERR_ARG;
     for (int j = 0; j < n_heads; j++) {
       const dba_upd_head_t &g = heads[j];
       const long long wbytes = (long long)g.k * c * 9 * isz, bbytes = (long long)g.k * isz;
       for (int o = 0; o < 2; o++) {
         const void *p = o ? (const void *)h.sum : (const void *)h.out;
         const long long pbytes = o ? sbytes : obytes;
-        if (overlaps(p, pbytes, g.x, xbytes) || overlaps(p, pbytes, g.weight, wbytes) || overlaps(p, pbytes, g.bias, bbytes))
+        if (ranges_overlap(p, pbytes, g.x, xbytes) || ranges_overlap(p, pbytes, g.weight, wbytes) ||
+            ranges_overlap(p, pbytes, g.bias, bbytes))
           return DBA_ERR_ARG;
-        if (j != i && (overlaps(p, pbytes, g.out, (long long)n * hw * g.k * isz) ||
-                       overlaps(p, pbytes, g.sum, (long long)n * hw * g.k * 4)))
+        if (j != i && (ranges_overlap(p, pbytes, g.out, (long long)n * hw * g.k * isz) ||
+                       ranges_overlap(p, pbytes, g.sum, (long long)n * hw * g.k * 4)))
           return DBA_ERR_ARG;
       }
     }

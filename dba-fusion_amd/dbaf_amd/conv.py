@@ -32,7 +32,6 @@ Arguments are checked on the host without synchronising; work is enqueued on tor
 torch's allocator only, and every call can be captured into a hipGraph.  CPU tensors raise.
 """
 import collections
-import ctypes
 
 import torch
 import torch.nn as nn
@@ -43,9 +42,11 @@ Packed = collections.namedtuple("Packed", "w bias")
 Pointwise = collections.namedtuple("Pointwise", "w bias c_in")   # w [C_out, ceil32(C_in)], the columns from c_in on zero
 
 
+_p = _lib.ptr
+
+
 def _require(cond, msg):
-    if not cond:
-        raise ValueError("conv3x3 (MI355X): " + msg)
+    _lib.require(cond, "conv3x3", msg)
 
 
 def supported(c0, c1, c_out):
@@ -67,28 +68,39 @@ def _pack(weights, biases):
     return Packed(w, b.to(torch.float16).contiguous())
 
 
-def pack_weights(conv_or_convs):
-    """-> Packed for one nn.Conv2d or a tuple of them (then concatenated along C_out).  The packed copy lives on the first
-    module and is rebuilt when any parameter's data_ptr() or _version changed (optimizer steps, load_state_dict, copy_); a
-    write through `.data` changes neither: call clear_pack_cache(module) after one.  During a stream capture nothing is
-    kept (the copy would live in the graph's pool) unless an eager call has packed before."""
+# what pack_weights (k = 3) and pack_pointwise (k = 1) say when they refuse a module
+_KINDS = {3: ("pack_weights", "only 3x3, stride 1, zero padding 1, one group"),
+          1: ("pack_pointwise", "only 1x1, stride 1, no padding, one group")}
+
+
+def _cached(conv_or_convs, slot, k, build):
+    """build(weights, biases) of one plain k x k nn.Conv2d or a tuple of them with one C_in.  The result lives on the first
+    module under `slot`, one entry per group of modules this one leads, and is rebuilt when any parameter's data_ptr() or
+    _version changed.  During a stream capture nothing is kept (the copy would live in the graph's pool) unless an eager
+    call has packed before."""
     convs = (conv_or_convs,) if isinstance(conv_or_convs, nn.Module) else tuple(conv_or_convs)
-    _require(len(convs) >= 1 and all(isinstance(m, nn.Conv2d) for m in convs), "pack_weights takes nn.Conv2d modules")
+    _require(len(convs) >= 1 and all(isinstance(m, nn.Conv2d) for m in convs), "%s takes nn.Conv2d modules" % _KINDS[k][0])
     for m in convs:
-        _require(m.kernel_size == (3, 3) and m.stride == (1, 1) and m.padding == (1, 1) and m.dilation == (1, 1)
-                 and m.groups == 1 and m.padding_mode == "zeros", "only 3x3, stride 1, zero padding 1, one group")
+        _require(_plain(m, k), _KINDS[k][1])
         _require(m.weight.is_cuda, "parameters must be on a HIP device; no CPU path")
         _require(m.in_channels == convs[0].in_channels, "concatenated convolutions must share C_in")
     ids = tuple(id(m) for m in convs)
     key = tuple((m.weight.data_ptr(), m.weight._version) + ((None, None) if m.bias is None else
                                                             (m.bias.data_ptr(), m.bias._version)) for m in convs)
-    slot = convs[0].__dict__.get("_dba_conv3x3", {})     # one entry per group of modules this one leads
-    kept = slot.get(ids)
+    kept = convs[0].__dict__.get(slot, {}).get(ids)
     if kept is None or kept[0] != key:
-        kept = (key, _pack([m.weight for m in convs], [m.bias for m in convs]))
+        kept = (key, build([m.weight for m in convs], [m.bias for m in convs]))
         if not torch.cuda.is_current_stream_capturing():
-            convs[0].__dict__.setdefault("_dba_conv3x3", slot)[ids] = kept
+            convs[0].__dict__.setdefault(slot, {})[ids] = kept
     return kept[1]
+
+
+def pack_weights(conv_or_convs):
+    """-> Packed for one nn.Conv2d or a tuple of them (then concatenated along C_out).  The packed copy lives on the first
+    module and is rebuilt when any parameter's data_ptr() or _version changed (optimizer steps, load_state_dict, copy_); a
+    write through `.data` changes neither: call clear_pack_cache(module) after one.  During a stream capture nothing is
+    kept (the copy would live in the graph's pool) unless an eager call has packed before."""
+    return _cached(conv_or_convs, "_dba_conv3x3", 3, _pack)
 
 
 def clear_pack_cache(module):
@@ -118,22 +130,7 @@ def pack_pointwise(conv_or_convs):
     C_out): w [C_out, ceil32(C_in)] half with a zero tail, bias [C_out] half or None, c_in.  Kept and rebuilt as
     pack_weights keeps its copies: on the first module, under the parameters' data_ptr() and _version; nothing is kept
     during a stream capture; clear_pack_cache forgets it."""
-    convs = (conv_or_convs,) if isinstance(conv_or_convs, nn.Module) else tuple(conv_or_convs)
-    _require(len(convs) >= 1 and all(isinstance(m, nn.Conv2d) for m in convs), "pack_pointwise takes nn.Conv2d modules")
-    for m in convs:
-        _require(_plain(m, 1), "only 1x1, stride 1, no padding, one group")
-        _require(m.weight.is_cuda, "parameters must be on a HIP device; no CPU path")
-        _require(m.in_channels == convs[0].in_channels, "concatenated convolutions must share C_in")
-    ids = tuple(id(m) for m in convs)
-    key = tuple((m.weight.data_ptr(), m.weight._version) + ((None, None) if m.bias is None else
-                                                            (m.bias.data_ptr(), m.bias._version)) for m in convs)
-    slot = convs[0].__dict__.get("_dba_conv1x1", {})
-    kept = slot.get(ids)
-    if kept is None or kept[0] != key:
-        kept = (key, _pack_pointwise([m.weight for m in convs], [m.bias for m in convs]))
-        if not torch.cuda.is_current_stream_capturing():
-            convs[0].__dict__.setdefault("_dba_conv1x1", slot)[ids] = kept
-    return kept[1]
+    return _cached(conv_or_convs, "_dba_conv1x1", 1, _pack_pointwise)
 
 
 def _half4(t, nm, dev=None):
@@ -147,6 +144,11 @@ def _half4(t, nm, dev=None):
 def _overlap(x, y):
     a, b = x.data_ptr(), y.data_ptr()
     return a < b + y.numel() * y.element_size() and b < a + x.numel() * x.element_size()
+
+
+def _bias_ok(bias, nm, c_out, dev):
+    _require(bias is None or (bias.is_cuda and bias.device == dev and bias.dtype == torch.float16 and bias.is_contiguous()
+                              and tuple(bias.shape) == (c_out,)), "%s must be a contiguous half [%d] on %s" % (nm, c_out, dev))
 
 
 def _inputs(x, weight, bias, x1, x1_first, x1_channels, c_out_of=None):
@@ -172,9 +174,7 @@ def _inputs(x, weight, bias, x1, x1_first, x1_channels, c_out_of=None):
     c_out = int(pk.w.shape[1])
     _require(int(pk.w.shape[2]) == c0 + c1, "the weights read %d channels, the input has %d + %d" % (pk.w.shape[2], c0, c1))
     _require(pk.w.data_ptr() % 16 == 0, "packed weights must be 16-byte aligned")
-    if pk.bias is not None:
-        _require(pk.bias.is_cuda and pk.bias.device == x.device and pk.bias.dtype == torch.float16 and pk.bias.is_contiguous()
-                 and tuple(pk.bias.shape) == (c_out,), "bias must be a contiguous half [%d] on %s" % (c_out, x.device))
+    _bias_ok(pk.bias, "bias", c_out, x.device)
     _require(supported(c0, c1, c_out), "channels must satisfy c0 %% 32 == 0, c1 %% 32 == 0, C_out %% 64 == 0; got %d, %d, %d"
              % (c0, c1, c_out))
     _require(h * w * max(c0 + c1, c1_total, c_out) < 2 ** 31, "one image's planes must stay below 2^31 elements")
@@ -182,26 +182,24 @@ def _inputs(x, weight, bias, x1, x1_first, x1_channels, c_out_of=None):
 
 
 def _src_args(x, c0, x1, c1, c1_total, first):
-    return (ctypes.c_void_p(x.data_ptr()), c0, ctypes.c_void_p(x1.data_ptr()) if x1 is not None else None, c1, c1_total, first)
+    return (_p(x), c0, _p(x1), c1, c1_total, first)
 
 
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _no_clobber(out, nm, x, x1, pk):
-    for t, tnm in ((x, "x"), (x1, "x1"), (pk.w, "the weights"), (pk.bias, "the bias")):
-        _require(t is None or not _overlap(out, t), "%s overlaps %s" % (nm, tnm))
+def _out(out, shape, x, reads):
+    """where a launch writes: a new half tensor `shape` on x's device, or the caller's `out`, which must be that and share no
+    byte with what the launch reads: `reads`, (tensor or None, its name) each"""
+    if out is None:
+        return torch.empty(shape, dtype=torch.float16, device=x.device)
+    _half4(out, "out", x.device)
+    _require(tuple(out.shape) == shape, "out must be %s, got %s" % (shape, tuple(out.shape)))
+    for t, tnm in reads:
+        _require(t is None or not _overlap(out, t), "out overlaps %s" % tnm)
+    return out
 
 
 def conv3x3(x, weight, bias=None, relu=False, x1=None, x1_first=0, x1_channels=None, out=None):
     pk, n, h, w, c0, c1, c1_total, first, c_out = _inputs(x, weight, bias, x1, x1_first, x1_channels)
-    if out is None:
-        out = torch.empty((n, c_out, h, w), dtype=torch.float16, device=x.device)
-    else:
-        _half4(out, "out", x.device)
-        _require(tuple(out.shape) == (n, c_out, h, w), "out must be %s, got %s" % ((n, c_out, h, w), tuple(out.shape)))
-        _no_clobber(out, "out", x, x1, pk)
+    out = _out(out, (n, c_out, h, w), x, ((x, "x"), (x1, "x1"), (pk.w, "the weights"), (pk.bias, "the bias")))
     with torch.cuda.device(x.device):
         _lib.check(_lib.load().dba_conv3x3_f16(*_src_args(x, c0, x1, c1, c1_total, first), _p(pk.w), _p(pk.bias), c_out, n, h, w,
                                                int(bool(relu)), _p(out), _lib.stream(x.device)), "dba_conv3x3_f16")
@@ -238,12 +236,9 @@ def conv3x3_blend(x, packed, gq, z, net, x1=None, x1_first=0, x1_channels=None, 
         _half4(t, nm, x.device)
         _require(tuple(t.shape) == (n, c, h, w), "%s must be %s, got %s" % (nm, (n, c, h, w), tuple(t.shape)))
     _gate_term(gq, "gq", x, n, c)
-    if out is None:
-        out = torch.empty_like(net)
-    else:
-        _half4(out, "out", x.device)
-        _require(tuple(out.shape) == (n, c, h, w), "out must be %s, got %s" % ((n, c, h, w), tuple(out.shape)))
-        _no_clobber(out, "out", x, x1, pk)
+    given = out is not None
+    out = _out(out, (n, c, h, w), x, ((x, "x"), (x1, "x1"), (pk.w, "the weights"), (pk.bias, "the bias")))
+    if given:
         _require(not _overlap(out, z) and not _overlap(out, gq), "out overlaps z or gq")
         _require(out.data_ptr() == net.data_ptr() or not _overlap(out, net), "out overlaps net without being net")
     with torch.cuda.device(x.device):
@@ -282,9 +277,7 @@ def _pointwise(weight, bias, dev, what="weight"):
              and 0 < pk.c_in <= pk.w.shape[1] == (pk.c_in + 31) // 32 * 32,
              "packed %s must be a contiguous half [C_out, ceil32(C_in)] on %s" % (what, dev))
     _require(pk.w.data_ptr() % 16 == 0, "packed %s must be 16-byte aligned" % what)
-    if pk.bias is not None:
-        _require(pk.bias.is_cuda and pk.bias.device == dev and pk.bias.dtype == torch.float16 and pk.bias.is_contiguous()
-                 and tuple(pk.bias.shape) == (c_out,), "the bias of %s must be a contiguous half [%d] on %s" % (what, c_out, dev))
+    _bias_ok(pk.bias, "the bias of %s" % what, c_out, dev)
     _require(c_out % 64 == 0, "C_out must be a multiple of 64, got %d" % c_out)
     return pk, c_out
 
@@ -297,13 +290,7 @@ def conv1x1(x, weight, bias=None, relu=False, out=None):
     pk, c_out = _pointwise(weight, bias, x.device)
     _require(pk.c_in == c_in, "the weights read %d channels, the input has %d" % (pk.c_in, c_in))
     _require(h * w * max(c_in, c_out) < 2 ** 31, "one image's planes must stay below 2^31 elements")
-    if out is None:
-        out = torch.empty((n, c_out, h, w), dtype=torch.float16, device=x.device)
-    else:
-        _half4(out, "out", x.device)
-        _require(tuple(out.shape) == (n, c_out, h, w), "out must be %s, got %s" % ((n, c_out, h, w), tuple(out.shape)))
-        for t, tnm in ((x, "x"), (pk.w, "the weights"), (pk.bias, "the bias")):
-            _require(t is None or not _overlap(out, t), "out overlaps %s" % tnm)
+    out = _out(out, (n, c_out, h, w), x, ((x, "x"), (pk.w, "the weights"), (pk.bias, "the bias")))
     with torch.cuda.device(x.device):
         _lib.check(_lib.load().dba_conv1x1_f16(_p(x), c_in, _p(pk.w), _p(pk.bias), c_out, n, h * w, int(bool(relu)), _p(out),
                                                _lib.stream(x.device)), "dba_conv1x1_f16")

@@ -42,13 +42,11 @@ MAX_SOURCES = 8
 _DTYPES = {torch.float32: _lib.DBA_F32, torch.float16: _lib.DBA_F16}
 
 
+_ptr, _overlap = _lib.ptr, _conv._overlap
+
+
 def _require(cond, msg):
-    if not cond:
-        raise ValueError("gru (MI355X): " + msg)
-
-
-def _ptr(x):
-    return ctypes.c_void_p(x.data_ptr())
+    _lib.require(cond, "gru", msg)
 
 
 def _planes(x, nm):
@@ -78,13 +76,8 @@ def _gate(g, nm, ref, n, c):
              "%s must be a contiguous [%d, %d, 1, 1], got %s" % (nm, n, c, tuple(g.shape)))
 
 
-def _overlap(x, y):
-    a, b = x.data_ptr(), y.data_ptr()
-    return a < b + y.numel() * y.element_size() and b < a + x.numel() * x.element_size()
-
-
 def _stream(x):
-    return ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+    return _lib.stream(x.device)
 
 
 def pack(net, *inputs, relu=()):
@@ -216,29 +209,42 @@ class ConvGRU(nn.Module):
             return False
         return True
 
+    def _gate_convs(self, c, ct, dev):
+        """what both fuse_conv routes ask of convz, convr and convq -> the three, or None: channel counts the kernels take
+        (c of the state, ct of the packed input) and plain 3x3s of ct channels answering in half on dev"""
+        gates = (self.convz, self.convr, self.convq)
+        ok = (_conv.supported(ct, 0, 2 * c) and _conv.supported(c, ct - c, c)
+              and all(_conv._plain(m, 3) and _conv._answers_half(m, dev) and m.in_channels == ct for m in gates))
+        return gates if ok else None
+
     def _conv_route(self, net, net_inp, gz):
         """the facts of the fuse_conv route beyond _fusable: half tensors, the three gate convolutions answering in half,
         channel counts the kernels take"""
-        c, ct = net.shape[1], net_inp.shape[1]
-        return (net.dtype == torch.float16 and gz.dtype == torch.float16 and _conv.supported(ct, 0, 2 * c)
-                and _conv.supported(c, ct - c, c) and all(_conv.conv_fusable(m, net_inp) for m in (self.convz, self.convr, self.convq)))
+        gates = self._gate_convs(net.shape[1], net_inp.shape[1], net_inp.device)
+        return (net.dtype == torch.float16 and gz.dtype == torch.float16 and _conv._half_map(net_inp) and gates is not None
+                and all(m.out_channels % 64 == 0 for m in gates))
 
     def _pointwise_route(self, net, inputs):
         """the facts of the route that calls no stock convolution, known before anything is enqueued: _conv_route's (on the
         channel counts pack will give), and w and the three *_glo plain 1x1s of c -> c channels answering in half"""
         c, ct, dev = net.shape[1], net.shape[1] + sum(int(x.shape[1]) for x in inputs), net.device
-        if net.dtype != torch.float16 or not (_conv.supported(ct, 0, 2 * c) and _conv.supported(c, ct - c, c)) or c > 1024:
+        gates = self._gate_convs(c, ct, dev)
+        if net.dtype != torch.float16 or gates is None or any(m.out_channels != c for m in gates) or c > 1024:
             return False
         if ct * net.shape[2] * net.shape[3] >= 2 ** 31:   # one image's packed planes: the kernels' int offsets
             return False
-        for m in (self.convz, self.convr, self.convq):
-            if not (_conv._plain(m, 3) and _conv._answers_half(m, dev) and m.in_channels == ct and m.out_channels == c):
-                return False
         for m in (self.w, self.convz_glo, self.convr_glo, self.convq_glo):
             if not (_conv._plain(m, 1) and _conv._answers_half(m, dev) and m.in_channels == c and m.out_channels == c):
                 return False
         biases = [m.bias is None for m in (self.convz_glo, self.convr_glo, self.convq_glo)]
         return all(biases) or not any(biases)
+
+    def _gates_blend(self, net, net_inp, gz, gr, gq):
+        """the tail of both fuse_conv routes: convz + convr + reset in one launch, convq + blend in another"""
+        c = net.shape[1]
+        z, rnet = _conv.conv3x3_gates(net_inp, _conv.pack_weights((self.convz, self.convr)), gz, gr, net)
+        return _conv.conv3x3_blend(rnet, _conv.pack_weights(self.convq), gq, z, net, x1=net_inp, x1_first=c,
+                                   x1_channels=net_inp.shape[1] - c)
 
     def forward(self, net, *inputs):
         return self._forward(net, tuple(inputs), ())
@@ -257,13 +263,10 @@ class ConvGRU(nn.Module):
                      % ("net" if k == 0 else "inputs[%d]" % (k - 1)))
         if self.fuse_conv and self._fusable(net, inputs) and self._pointwise_route(net, inputs):
             # no stock convolution: w(net), the context and the three *_glo 1x1s are conv1x1_context's two launches
-            c = net.shape[1]
             net_inp = pack(net, *inputs, relu=((False,) + relu) if any(relu) else ())
             glo, gz, gr, gq = context(_conv.pack_pointwise(self.w), net,
                                       _conv.pack_pointwise((self.convz_glo, self.convr_glo, self.convq_glo)))
-            z, rnet = _conv.conv3x3_gates(net_inp, _conv.pack_weights((self.convz, self.convr)), gz, gr, net)
-            return _conv.conv3x3_blend(rnet, _conv.pack_weights(self.convq), gq, z, net, x1=net_inp, x1_first=c,
-                                       x1_channels=net_inp.shape[1] - c)
+            return self._gates_blend(net, net_inp, gz, gr, gq)
         a = self.w(net)
         # autocast may answer in another dtype than the inputs': then the statements' own promotion rules apply
         if not self._fusable(net, inputs) or a.dtype != net.dtype:
@@ -276,10 +279,7 @@ class ConvGRU(nn.Module):
 
         gz, gr, gq = self.convz_glo(glo), self.convr_glo(glo), self.convq_glo(glo)
         if self.fuse_conv and self._conv_route(net, net_inp, gz):
-            c = net.shape[1]
-            z, rnet = _conv.conv3x3_gates(net_inp, _conv.pack_weights((self.convz, self.convr)), gz, gr, net)
-            return _conv.conv3x3_blend(rnet, _conv.pack_weights(self.convq), gq, z, net, x1=net_inp, x1_first=c,
-                                       x1_channels=net_inp.shape[1] - c)
+            return self._gates_blend(net, net_inp, gz, gr, gq)
         cz = self.convz(net_inp)
         cr = self.convr(net_inp)
         reset_(net_inp, cr, gr, net)    # net_inp is cat([r*net, inp], 1) from here on; convz and convr are enqueued
