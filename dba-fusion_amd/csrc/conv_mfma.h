@@ -7,7 +7,8 @@
 // what the kernel's guard refuses is written as zero and never dereferenced.  That gather stays spelled out in each kernel:
 // 3x3 guards on a precomputed offset, 1x1 on pixel and channel, and every shared form of it tried moved the register
 // allocation of both.  The kernels also keep their own tiles, staging maps, loops and epilogue bodies; every result they store
-// is rounded by mf_round and nowhere else.
+// is rounded by mf_round and nowhere else.  conv7x7.hip (four input channels) uses the wave's place, the accumulators, the
+// epilogue's statements and the launch; its K is a kernel row of 8 tap slots x 4 channels and its LDS image is its own.
 #pragma once
 #include "common.h"
 

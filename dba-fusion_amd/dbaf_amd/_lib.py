@@ -207,6 +207,8 @@ SYMBOLS = {
     "dba_conv1x1_f16": (c_int, [_P, c_int, _P, _P] + [c_int] * 4 + [_P, _P]),
     "dba_conv1x1_context_workspace_bytes": (c_size_t, [c_int] * 3),
     "dba_conv1x1_context_f16": (c_int, [_P] * 5 + [c_int] * 3 + [_P, c_size_t] + [_P] * 5),
+    "dba_conv7x7_tile": (c_int, []),
+    "dba_conv7x7_f16": (c_int, [_P, c_int, _P, _P] + [c_int] * 5 + [_P, _P]),
     "dba_enc_norm": (c_int, [_P, c_int, c_int, c_float, c_int, c_int, _P, _P, _P]),
     "dba_enc_norm_skip": (c_int, [_P, _P, _P, c_int, c_int, c_float, c_int, _P, _P, _P, _P]),
     "dba_enc_relu_skip": (c_int, [_P, _P, ctypes.c_longlong, c_int, _P, _P]),

@@ -1,5 +1,6 @@
 """3x3 convolutions of half tensors on the MI355X's matrix cores (csrc/conv3x3.hip), with the ConvGRU's gate arithmetic in
-the epilogue.  Opt-in: ConvGRU.fuse_conv / UpdateModule.fuse_conv route through here, nothing else does.
+the epilogue.  Opt-in: ConvGRU.fuse_conv / UpdateModule.fuse_conv route through here, and UpdateModule.fuse_flow_stem for
+the 7x7 flow stem; nothing else does.
 
   pack_weights(conv_or_convs)        the parameters of one nn.Conv2d(C_in, C_out, 3, padding=1), or of several with one C_in
                                      one behind the other along C_out, as the kernels read them: Packed(w [9, C_out, C_in]
@@ -22,7 +23,17 @@ and the 1x1 convolutions as a GEMM on the same matrix instruction (csrc/conv1x1.
                                      F.conv2d(x, weight, bias) for a 1x1 weight, optionally torch.relu behind it
   conv1x1_context(net, packed_w, packed_glo)       -> (glo, gz, gr, gq): w(net), the ConvGRU's context mean and the three
                                      *_glo 1x1s in two launches; w(net) is never written
-  conv_fusable / pointwise_fusable   the routing facts of one nn.Conv2d on x
+
+and the 7x7 flow stem, a convolution of FOUR channels, on the same matrix instruction (csrc/conv7x7.hip); C_out % 64 == 0:
+
+  pack_stem(conv)                    Stem(w [7, C_out, 32] half: entry [ky, o, 4 kx + i] = weight[o, i, ky, kx], the eighth
+                                     slot of a kernel row zero; bias), cached as above
+  conv7x7(x, weight, bias=None, relu=False, out=None)
+                                     F.conv2d(x.half(), weight, bias, padding=3) for x [n, 4, h, w] of float16 OR float32,
+                                     optionally torch.relu behind it: a float32 x is rounded to half as the kernel reads it
+                                     (the bytes of autocast's cast, without its launch)
+
+  conv_fusable / pointwise_fusable / stem_fusable      the routing facts of one nn.Conv2d on x
 
 Numerics: a float32 sum in one fixed order, plus the bias in float32, rounded ONCE to half; the gate statements behind it
 round as dbaf_amd.gru.reset_ / blend do.  MIOpen's half convolution rounds differently, so results differ from nn.Conv2d's
@@ -40,6 +51,7 @@ from . import _lib
 
 Packed = collections.namedtuple("Packed", "w bias")
 Pointwise = collections.namedtuple("Pointwise", "w bias c_in")   # w [C_out, ceil32(C_in)], the columns from c_in on zero
+Stem = collections.namedtuple("Stem", "w bias")                  # w [7, C_out, 32]: [ky, o, 4 kx + i], the slots of kx = 7 zero
 
 
 _p = _lib.ptr
@@ -68,9 +80,10 @@ def _pack(weights, biases):
     return Packed(w, b.to(torch.float16).contiguous())
 
 
-# what pack_weights (k = 3) and pack_pointwise (k = 1) say when they refuse a module
+# what pack_weights (k = 3), pack_pointwise (k = 1) and pack_stem (k = 7) say when they refuse a module
 _KINDS = {3: ("pack_weights", "only 3x3, stride 1, zero padding 1, one group"),
-          1: ("pack_pointwise", "only 1x1, stride 1, no padding, one group")}
+          1: ("pack_pointwise", "only 1x1, stride 1, no padding, one group"),
+          7: ("pack_stem", "only 7x7, stride 1, zero padding 3, one group")}
 
 
 def _cached(conv_or_convs, slot, k, build):
@@ -107,6 +120,7 @@ def clear_pack_cache(module):
     for m in module.modules():
         m.__dict__.pop("_dba_conv3x3", None)
         m.__dict__.pop("_dba_conv1x1", None)
+        m.__dict__.pop("_dba_conv7x7", None)
 
 
 def pointwise_tile():
@@ -320,6 +334,61 @@ def conv1x1_context(net, packed_w, packed_glo):
     return tuple(outs)
 
 
+def stem_tile():
+    """the side of a workgroup's square pixel tile of the 7x7 kernel"""
+    return int(_lib.load().dba_conv7x7_tile())
+
+
+def _pack_stem(weights, biases):
+    _require(len(weights) == 1, "pack_stem takes one convolution")
+    w, b = weights[0].detach(), biases[0]
+    _require(w.dim() == 4 and tuple(w.shape[1:]) == (4, 7, 7), "the stem's weight must be [C_out, 4, 7, 7], got %s" % (tuple(w.shape),))
+    wp = torch.zeros((7, int(w.shape[0]), 8, 4), dtype=torch.float16, device=w.device)
+    wp[:, :, :7, :] = w.permute(2, 0, 3, 1)        # [ky, o, kx, i]
+    return Stem(wp.view(7, int(w.shape[0]), 32), None if b is None else b.detach().to(torch.float16).contiguous())
+
+
+def pack_stem(conv):
+    """-> Stem for one nn.Conv2d(4, C_out, 7, padding=3): w [7, C_out, 32] half with entry [ky, o, 4 kx + i] = weight[o, i,
+    ky, kx] and the four slots of kx = 7 zero, bias [C_out] half or None.  Kept and rebuilt as pack_weights keeps its
+    copies: on the module, under the parameters' data_ptr() and _version; nothing is kept during a stream capture;
+    clear_pack_cache forgets it."""
+    return _cached(conv, "_dba_conv7x7", 7, _pack_stem)
+
+
+_STEM_DTYPES = {torch.float16: _lib.DBA_F16, torch.float32: _lib.DBA_F32}
+
+
+def conv7x7(x, weight, bias=None, relu=False, out=None):
+    """F.conv2d(x.half(), weight, bias, padding=3) for a [C_out, 4, 7, 7] weight, optionally with torch.relu behind it.
+    x [n, 4, h, w] contiguous, float16 or float32 (then rounded to half as it is read: no cast launch); weight: a Stem
+    (pack_stem) or the module's [C_out, 4, 7, 7]; C_out % 64 == 0.  -> half [n, C_out, h, w]"""
+    _require(isinstance(x, torch.Tensor) and x.is_cuda, "x must be a HIP device tensor; no CPU path")
+    _require(x.dtype in _STEM_DTYPES, "x must be float16 or float32, got %s" % x.dtype)
+    _require(x.dim() == 4 and x.numel() > 0 and x.is_contiguous() and x.shape[1] == 4,
+             "x must be a non-empty contiguous [n, 4, h, w], got %s" % (tuple(x.shape),))
+    n, _, h, w = (int(s) for s in x.shape)
+    if isinstance(weight, Stem):
+        pk = weight if bias is None else Stem(weight.w, bias)
+    else:
+        _require(isinstance(weight, torch.Tensor) and weight.is_cuda and weight.dim() == 4 and tuple(weight.shape[1:]) == (4, 7, 7),
+                 "weight must be a Stem or a device tensor [C_out, 4, 7, 7]")
+        pk = _pack_stem([weight], [bias])
+    _require(isinstance(pk.w, torch.Tensor) and pk.w.is_cuda and pk.w.device == x.device and pk.w.dtype == torch.float16
+             and pk.w.is_contiguous() and pk.w.dim() == 3 and pk.w.shape[0] == 7 and pk.w.shape[2] == 32,
+             "packed weights must be a contiguous half [7, C_out, 32] on %s" % x.device)
+    c_out = int(pk.w.shape[1])
+    _require(pk.w.data_ptr() % 16 == 0, "packed weights must be 16-byte aligned")
+    _bias_ok(pk.bias, "bias", c_out, x.device)
+    _require(c_out > 0 and c_out % 64 == 0, "C_out must be a multiple of 64, got %d" % c_out)
+    _require(h * w * c_out < 2 ** 31, "one image's planes must stay below 2^31 elements")
+    out = _out(out, (n, c_out, h, w), x, ((x, "x"), (pk.w, "the weights"), (pk.bias, "the bias")))
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().dba_conv7x7_f16(_p(x), _STEM_DTYPES[x.dtype], _p(pk.w), _p(pk.bias), c_out, n, h, w,
+                                               int(bool(relu)), _p(out), _lib.stream(x.device)), "dba_conv7x7_f16")
+    return out
+
+
 def _plain(conv, k):
     """a k x k convolution of stride 1 with zero padding k // 2, no dilation, one group"""
     return (conv.kernel_size == (k, k) and conv.stride == (1, 1) and conv.padding == (k // 2, k // 2) and conv.dilation == (1, 1)
@@ -348,3 +417,15 @@ def pointwise_fusable(conv, x):
     """conv_fusable for a 1x1 convolution: any C_in, C_out a multiple of 64"""
     return (_half_map(x) and _answers_half(conv, x.device) and _plain(conv, 1) and conv.out_channels % 64 == 0
             and x.shape[1] == conv.in_channels and x.shape[2] * x.shape[3] * max(x.shape[1], conv.out_channels) < 2 ** 31)
+
+
+def stem_fusable(conv, x):
+    """conv_fusable for the 7x7 flow stem: four input channels, C_out a multiple of 64; x half, or float32 while autocast to
+    half is on (the kernel rounds it as autocast's cast would)"""
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dim() == 4 and x.is_contiguous() and x.numel() > 0):
+        return False
+    if not (_plain(conv, 7) and _answers_half(conv, x.device) and conv.in_channels == 4 and conv.out_channels % 64 == 0
+            and x.shape[1] == 4):
+        return False
+    casts = x.dtype == torch.float32 and torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.float16
+    return (x.dtype == torch.float16 or casts) and x.shape[2] * x.shape[3] * conv.out_channels < 2 ** 31

@@ -41,6 +41,11 @@ conv3x3_pair launch that writes two plain contiguous [n, 128, ht, wd] tensors, w
 ReLU of half(c) is the reference's in-place ReLU).  With the flag, a forward with upsample=False then makes one stock
 convolution call, the 7x7 flow stem.  Each piece routes on its own facts; where they fail, that piece alone keeps the
 stock route.
+
+fuse_flow_stem (default off: then nothing changes; independent of fuse_conv) routes flow_encoder[0] with its ReLU through
+dbaf_amd.conv.conv7x7: ONE launch in place of the stem on MIOpen, the in-place ReLU behind it and, where the caller hands a
+float32 flow under autocast (CorrBlock.lookup_motion does), autocast's cast in front of it -- the kernel rounds the float32
+values to half as it reads them.  With both switches a forward with upsample=False makes no stock convolution call.
 """
 import ctypes
 
@@ -358,8 +363,12 @@ class UpdateModule(nn.Module):
     def fuse_upmask(self, on):
         self.agg.fuse_upmask = bool(on)
 
+    # flow_encoder[0] with its ReLU as ONE dbaf_amd.conv.conv7x7 launch where stem_fusable holds; a switch of its own,
+    # independent of fuse_conv
+    fuse_flow_stem = False
+
     # the convolutions on the matrix cores (dbaf_amd.conv): the whole GRU, corr_encoder[0] / [2], flow_encoder[2], the
-    # heads' delta[0] / weight[0] and the aggregation's conv1 / conv2; the 7x7 flow stem stays on MIOpen
+    # heads' delta[0] / weight[0] and the aggregation's conv1 / conv2; the 7x7 flow stem has its own switch, fuse_flow_stem
     @property
     def fuse_conv(self):
         return self.gru.fuse_conv
@@ -431,7 +440,11 @@ class UpdateModule(nn.Module):
         else:
             corr = ce[1](ce[0](corr))
         corr = self._conv3(ce[2], corr, asks)
-        flow = self._conv3(fe[2], fe[1](fe[0](flow)), asks)
+        if self.fuse_flow_stem and not asks and _conv.stem_fusable(fe[0], flow):
+            flow = _conv.conv7x7(flow, _conv.pack_stem(fe[0]), relu=True)   # a float32 flow under autocast: rounded as it is read
+        else:
+            flow = fe[1](fe[0](flow))
+        flow = self._conv3(fe[2], flow, asks)
         if (not asks and _dense(net) and corr.dtype == net.dtype and flow.dtype == net.dtype and inp.dtype == net.dtype
                 and inp.is_contiguous()):
             net = self.gru.forward_relu(net, (inp, corr, flow), relu=(False, True, True))

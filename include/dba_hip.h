@@ -1028,6 +1028,27 @@ int dba_conv1x1_context_f16(const void *net, const void *weight, const void *bia
                             int c, int n, int hw, void *workspace, size_t workspace_bytes, void *glo, void *gz, void *gr,
                             void *gq, dba_stream_t stream);
 
+/* ---- 7x7 convolution of four channels on the matrix cores: the update operator's flow stem (csrc/conv7x7.hip) -----------
+ * nn.Conv2d(4, C_out, 7, padding=3) on x [n, 4, h, w] (dbaf/droid_net.py:85-86): a GEMM on mfma_f32_16x16x32_f16 whose K is
+ * one kernel row, 7 taps and one zero slot of 4 channels each,
+ *   c[n, o, y, x] = half(sum_{i, ky, kx} W[o, i, ky, kx] * half(x[n, i, y + ky - 3, x + kx - 3]) + float(b[o])),
+ * zeros outside the map; a float32 sum in one fixed order (kernel rows ky = 0 .. 6 ascending, the hardware's order inside an
+ * MFMA; no atomics: the same bits on every run), ONE rounding.  C_in is 4 and nothing else, C_out a multiple of 64.
+ *   x        dtype = DBA_F16 or DBA_F32, aligned to an element.  A float32 value is rounded to half as it is read (to nearest
+ *            even, beyond 65504 to infinity): the bytes of x.to(torch.float16), without that launch.
+ *   weight   [7][C_out][32] half, entry [ky][o][4 kx + i] = W[o, i, ky, kx] for kx < 7 and ZERO for kx = 7, 16-byte aligned.
+ *            bias [C_out] half or NULL.  No load touches an address outside x, weight and bias.
+ *   The eighth slot of a kernel row lies on the pixel right of the footprint; the kernel feeds the matrix core zeros there,
+ *   so a NaN or an infinity of the input reaches exactly the outputs whose 7x7 window holds it.
+ * dba_conv7x7_f16: out [n, c_out, h, w] half = c, or torch.relu(c) when relu != 0 (NaN stays, -0 -> +0).  One launch.
+ * Refused without a launch, DBA_ERR_ARG: an extent <= 0, C_out % 64 != 0, a dtype other than the two, a null pointer (bias
+ * excepted), a misaligned pointer, h * w * C_out of one image or the grid beyond 2^31 - 1, an output that shares a byte with
+ * an input.
+ * dba_conv7x7_tile: the side of a workgroup's square pixel tile. */
+int dba_conv7x7_tile(void);
+int dba_conv7x7_f16(const void *x, int dtype, const void *weight, const void *bias, int c_out, int n, int h, int w, int relu,
+                    void *out, dba_stream_t stream);
+
 /* ---- Encoder glue (csrc/extractor.hip) -----------------------------------------------------------------------------
  * What the feature and context encoders (dbaf/modules/extractor.py:47-55, :183-198) and their caller
  * (dbaf/motion_filter.py:29-30, :35-36, :64-65) run between the convolutions, which stay with the caller.  Tensors are
