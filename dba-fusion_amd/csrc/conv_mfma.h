@@ -9,6 +9,8 @@
 // allocation of both.  The kernels also keep their own tiles, staging maps, loops and epilogue bodies; every result they store
 // is rounded by mf_round and nowhere else.  conv7x7.hip (four input channels) uses the wave's place, the accumulators, the
 // epilogue's statements and the launch; its K is a kernel row of 8 tap slots x 4 channels and its LDS image is its own.
+// conv_enc.hip (the encoders: stride 1 or 2, C_out % 32 == 0, a 7x7 stem of three channels) uses the fragment, the epilogue's
+// statements and the grid limits; its tiles, its division of a workgroup's waves and its launches are its own.
 #pragma once
 #include "common.h"
 

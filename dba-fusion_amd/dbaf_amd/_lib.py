@@ -209,6 +209,12 @@ SYMBOLS = {
     "dba_conv1x1_context_f16": (c_int, [_P] * 5 + [c_int] * 3 + [_P, c_size_t] + [_P] * 5),
     "dba_conv7x7_tile": (c_int, []),
     "dba_conv7x7_f16": (c_int, [_P, c_int, _P, _P] + [c_int] * 5 + [_P, _P]),
+    "dba_conv3x3s_tile_rows": (c_int, [c_int]),
+    "dba_conv3x3s_tile_cols": (c_int, []),
+    "dba_conv7x7s2_tile": (c_int, []),
+    "dba_conv3x3s_f16": (c_int, [_P, _P, _P] + [c_int] * 7 + [_P, _P]),
+    "dba_conv3x3s_down_f16": (c_int, [_P] * 4 + [c_int] * 6 + [_P, _P, _P]),
+    "dba_conv7x7s2_f16": (c_int, [_P, c_int, _P, _P] + [c_int] * 5 + [_P, _P]),
     "dba_enc_norm": (c_int, [_P, c_int, c_int, c_float, c_int, c_int, _P, _P, _P]),
     "dba_enc_norm_skip": (c_int, [_P, _P, _P, c_int, c_int, c_float, c_int, _P, _P, _P, _P]),
     "dba_enc_relu_skip": (c_int, [_P, _P, ctypes.c_longlong, c_int, _P, _P]),

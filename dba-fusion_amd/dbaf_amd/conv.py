@@ -35,6 +35,22 @@ and the 7x7 flow stem, a convolution of FOUR channels, on the same matrix instru
 
   conv_fusable / pointwise_fusable / stem_fusable      the routing facts of one nn.Conv2d on x
 
+and the encoders' convolutions (csrc/conv_enc.hip), behind BasicEncoder.fuse_conv / ResidualBlock.fuse_conv; C_in % 32 == 0
+and C_out % 32 == 0 for the 3x3s, C_out % 32 == 0 for the stem:
+
+  pack_strided(conv)                 Packed for one nn.Conv2d(C_in, C_out, 3, stride=1 or 2, padding=1), cached as above
+  pack_down(conv1, down_conv)        PackedDown(w [10, C_out, C_in]: conv1's nine taps, then the 1x1 stride-2 weight; bias,
+                                     bias_down) for a stride-2 block's conv1 and downsample[0], cached on conv1
+  pack_encoder_stem(conv)            EncStem(w [7, C_out, 32]: entry [ky, o, 4 kx + i] = weight[o, i, ky, kx], the slots of
+                                     kx = 7 and of i = 3 zero; bias) for nn.Conv2d(3, C_out, 7, stride=2, padding=3), cached
+  conv3x3s(x, packed, stride=1, relu=False, out=None)      F.conv2d(x, weight, bias, stride=stride, padding=1)
+  conv3x3s_down(x, packed, relu=False) -> (y, d)           conv1(x) (through torch.relu when relu) and downsample[0](x), one
+                                     launch; d never takes the ReLU
+  conv7x7s2(x, packed, relu=False, out=None)               F.conv2d(x.half(), weight, bias, stride=2, padding=3) for x
+                                     [n, 3, h, w] of float16 OR float32
+  strided_fusable / down_fusable / encoder_stem_fusable    the routing facts, pure functions of metadata
+The packs turn float32 parameters into half ONCE per parameter version: under autocast that replaces the per-call casts.
+
 Numerics: a float32 sum in one fixed order, plus the bias in float32, rounded ONCE to half; the gate statements behind it
 round as dbaf_amd.gru.reset_ / blend do.  MIOpen's half convolution rounds differently, so results differ from nn.Conv2d's
 in last half bits: the yardstick is the float64 statement (tests/conv3x3_cases.py).
@@ -52,6 +68,8 @@ from . import _lib
 Packed = collections.namedtuple("Packed", "w bias")
 Pointwise = collections.namedtuple("Pointwise", "w bias c_in")   # w [C_out, ceil32(C_in)], the columns from c_in on zero
 Stem = collections.namedtuple("Stem", "w bias")                  # w [7, C_out, 32]: [ky, o, 4 kx + i], the slots of kx = 7 zero
+PackedDown = collections.namedtuple("PackedDown", "w bias bias_down")   # w [10, C_out, C_in]: nine taps, then the 1x1 slice
+EncStem = collections.namedtuple("EncStem", "w bias")            # w [7, C_out, 32]: the slots of kx = 7 and of i = 3 zero
 
 
 _p = _lib.ptr
@@ -97,6 +115,11 @@ def _cached(conv_or_convs, slot, k, build):
         _require(_plain(m, k), _KINDS[k][1])
         _require(m.weight.is_cuda, "parameters must be on a HIP device; no CPU path")
         _require(m.in_channels == convs[0].in_channels, "concatenated convolutions must share C_in")
+    return _keep(convs, slot, build)
+
+
+def _keep(convs, slot, build):
+    """build(weights, biases) for the modules `convs`, kept on the first one under `slot` as _cached says"""
     ids = tuple(id(m) for m in convs)
     key = tuple((m.weight.data_ptr(), m.weight._version) + ((None, None) if m.bias is None else
                                                             (m.bias.data_ptr(), m.bias._version)) for m in convs)
@@ -121,6 +144,7 @@ def clear_pack_cache(module):
         m.__dict__.pop("_dba_conv3x3", None)
         m.__dict__.pop("_dba_conv1x1", None)
         m.__dict__.pop("_dba_conv7x7", None)
+        m.__dict__.pop("_dba_conv_enc", None)
 
 
 def pointwise_tile():
@@ -429,3 +453,182 @@ def stem_fusable(conv, x):
         return False
     casts = x.dtype == torch.float32 and torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.float16
     return (x.dtype == torch.float16 or casts) and x.shape[2] * x.shape[3] * conv.out_channels < 2 ** 31
+
+
+# ---- the encoders' convolutions (csrc/conv_enc.hip) ------------------------------------------------------------------------
+
+def _geometry(conv, k, strides):
+    """a k x k convolution with zero padding k // 2 and a stride in `strides`, no dilation, one group"""
+    return (isinstance(conv, nn.Conv2d) and conv.kernel_size == (k, k) and conv.stride[0] == conv.stride[1]
+            and conv.stride[0] in strides and conv.padding == (k // 2, k // 2) and conv.dilation == (1, 1) and conv.groups == 1
+            and conv.padding_mode == "zeros")
+
+
+def _on_device(convs, what):
+    for m in convs:
+        _require(m.weight.is_cuda, "%s: parameters must be on a HIP device; no CPU path" % what)
+
+
+def strided_tile(stride):
+    """(rows, columns) of a workgroup's tile of OUTPUT pixels of conv3x3s at this stride"""
+    lib = _lib.load()
+    return int(lib.dba_conv3x3s_tile_rows(int(stride))), int(lib.dba_conv3x3s_tile_cols())
+
+
+def encoder_stem_tile():
+    """the side of a workgroup's square tile of output pixels of conv7x7s2"""
+    return int(_lib.load().dba_conv7x7s2_tile())
+
+
+def pack_strided(conv):
+    """-> Packed for one nn.Conv2d(C_in, C_out, 3, stride=1 or 2, padding=1): pack_weights' layout and cache rules (on the
+    module, rebuilt when a parameter's data_ptr() or _version moves, nothing kept during a stream capture)"""
+    _require(_geometry(conv, 3, (1, 2)), "pack_strided: only 3x3, stride 1 or 2, zero padding 1, one group")
+    _on_device((conv,), "pack_strided")
+    return _keep((conv,), "_dba_conv_enc", _pack)
+
+
+def _pack_down(weights, biases):
+    w3, w1 = (t.detach() for t in weights)
+    c_out, c_in = int(w3.shape[0]), int(w3.shape[1])
+    w = torch.empty((10, c_out, c_in), dtype=torch.float16, device=w3.device)
+    w[:9] = w3.permute(2, 3, 0, 1).reshape(9, c_out, c_in)
+    w[9] = w1.reshape(c_out, c_in)
+    b3, b1 = (None if b is None else b.detach().to(torch.float16).contiguous() for b in biases)
+    return PackedDown(w, b3, b1)
+
+
+def pack_down(conv1, down_conv):
+    """-> PackedDown for a stride-2 block's conv1 = nn.Conv2d(C_in, C_out, 3, stride=2, padding=1) and its downsample[0] =
+    nn.Conv2d(C_in, C_out, 1, stride=2): w [10, C_out, C_in], conv1's nine taps and the 1x1 weight behind them; the two
+    biases apart.  Kept on conv1 under pack_weights' rules, over the parameters of both."""
+    _require(_geometry(conv1, 3, (2,)) and _geometry(down_conv, 1, (2,)),
+             "pack_down: a 3x3 stride-2 padding-1 convolution and a 1x1 stride-2 one, one group each")
+    _require(conv1.in_channels == down_conv.in_channels and conv1.out_channels == down_conv.out_channels,
+             "pack_down: the two convolutions must share C_in and C_out")
+    _on_device((conv1, down_conv), "pack_down")
+    return _keep((conv1, down_conv), "_dba_conv_enc", _pack_down)
+
+
+def _pack_encoder_stem(weights, biases):
+    w, b = weights[0].detach(), biases[0]
+    wp = torch.zeros((7, int(w.shape[0]), 8, 4), dtype=torch.float16, device=w.device)
+    wp[:, :, :7, :3] = w.permute(2, 0, 3, 1)       # [ky, o, kx, i]
+    return EncStem(wp.view(7, int(w.shape[0]), 32), None if b is None else b.detach().to(torch.float16).contiguous())
+
+
+def pack_encoder_stem(conv):
+    """-> EncStem for one nn.Conv2d(3, C_out, 7, stride=2, padding=3): w [7, C_out, 32] half with entry [ky, o, 4 kx + i] =
+    weight[o, i, ky, kx], the slots of kx = 7 and of i = 3 zero; bias [C_out] half or None.  Cached as pack_weights' copies."""
+    _require(_geometry(conv, 7, (2,)) and conv.in_channels == 3, "pack_encoder_stem: only 7x7, stride 2, zero padding 3, 3 -> C_out")
+    _on_device((conv,), "pack_encoder_stem")
+    return _keep((conv,), "_dba_conv_enc", _pack_encoder_stem)
+
+
+def _enc_weights(pk, kind, slices, x, c_in):
+    """the packed weights of conv3x3s (9 slices) / conv3x3s_down (10), checked -> c_out"""
+    _require(isinstance(pk, kind), "the weights must be a %s" % kind.__name__)
+    w = pk.w
+    _require(isinstance(w, torch.Tensor) and w.is_cuda and w.device == x.device and w.dtype == torch.float16 and w.is_contiguous()
+             and w.dim() == 3 and w.shape[0] == slices, "packed weights must be a contiguous half [%d, C_out, C_in] on %s"
+             % (slices, x.device))
+    c_out = int(w.shape[1])
+    _require(int(w.shape[2]) == c_in, "the weights read %d channels, the input has %d" % (w.shape[2], c_in))
+    _require(w.data_ptr() % 16 == 0, "packed weights must be 16-byte aligned")
+    _require(c_in % 32 == 0 and c_out > 0 and c_out % 32 == 0, "channels must satisfy C_in %% 32 == 0, C_out %% 32 == 0; got %d, %d"
+             % (c_in, c_out))
+    return c_out
+
+
+def _half_out(extent, stride):
+    return (extent - 1) // stride + 1
+
+
+def conv3x3s(x, packed, stride=1, relu=False, out=None):
+    """F.conv2d(x, weight, bias, stride=stride, padding=1) for packed = pack_strided(conv) (or any Packed), stride 1 or 2,
+    optionally with torch.relu behind it.  x [n, C_in, h, w] half, C_in % 32 == 0, C_out % 32 == 0.
+    -> half [n, C_out, (h - 1) // stride + 1, (w - 1) // stride + 1]"""
+    _half4(x, "x")
+    _require(stride in (1, 2), "stride must be 1 or 2, got %r" % (stride,))
+    n, c_in, h, w = (int(s) for s in x.shape)
+    c_out = _enc_weights(packed, Packed, 9, x, c_in)
+    _bias_ok(packed.bias, "bias", c_out, x.device)
+    _require(h * w * max(c_in, c_out) < 2 ** 31, "one image's planes must stay below 2^31 elements")
+    out = _out(out, (n, c_out, _half_out(h, stride), _half_out(w, stride)), x,
+               ((x, "x"), (packed.w, "the weights"), (packed.bias, "the bias")))
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().dba_conv3x3s_f16(_p(x), _p(packed.w), _p(packed.bias), c_in, c_out, n, h, w, int(stride),
+                                                int(bool(relu)), _p(out), _lib.stream(x.device)), "dba_conv3x3s_f16")
+    return out
+
+
+def conv3x3s_down(x, packed, relu=False):
+    """packed: pack_down(conv1, downsample[0]) of a stride-2 block.  -> (y, d): y = conv1(x), through torch.relu when relu,
+    the bytes of conv3x3s(x, ., stride=2, relu); d = downsample[0](x), never through the ReLU.  One launch, x read once; new
+    contiguous tensors [n, C_out, (h - 1) // 2 + 1, (w - 1) // 2 + 1]"""
+    _half4(x, "x")
+    n, c_in, h, w = (int(s) for s in x.shape)
+    c_out = _enc_weights(packed, PackedDown, 10, x, c_in)
+    _bias_ok(packed.bias, "bias", c_out, x.device)
+    _bias_ok(packed.bias_down, "bias_down", c_out, x.device)
+    _require(h * w * max(c_in, c_out) < 2 ** 31, "one image's planes must stay below 2^31 elements")
+    y = torch.empty((n, c_out, _half_out(h, 2), _half_out(w, 2)), dtype=torch.float16, device=x.device)
+    d = torch.empty_like(y)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().dba_conv3x3s_down_f16(_p(x), _p(packed.w), _p(packed.bias), _p(packed.bias_down), c_in, c_out, n,
+                                                     h, w, int(bool(relu)), _p(y), _p(d), _lib.stream(x.device)),
+                   "dba_conv3x3s_down_f16")
+    return y, d
+
+
+def conv7x7s2(x, packed, relu=False, out=None):
+    """F.conv2d(x.half(), weight, bias, stride=2, padding=3) for packed = pack_encoder_stem(conv) (or any EncStem),
+    optionally with torch.relu behind it.  x [n, 3, h, w] contiguous, float16 or float32 (then rounded to half as it is
+    read: no cast launch); C_out % 32 == 0.  -> half [n, C_out, (h - 1) // 2 + 1, (w - 1) // 2 + 1]"""
+    _require(isinstance(x, torch.Tensor) and x.is_cuda, "x must be a HIP device tensor; no CPU path")
+    _require(x.dtype in _STEM_DTYPES, "x must be float16 or float32, got %s" % x.dtype)
+    _require(x.dim() == 4 and x.numel() > 0 and x.is_contiguous() and x.shape[1] == 3,
+             "x must be a non-empty contiguous [n, 3, h, w], got %s" % (tuple(x.shape),))
+    n, _, h, w = (int(s) for s in x.shape)
+    _require(isinstance(packed, EncStem), "the weights must be an EncStem")
+    pw = packed.w
+    _require(isinstance(pw, torch.Tensor) and pw.is_cuda and pw.device == x.device and pw.dtype == torch.float16
+             and pw.is_contiguous() and pw.dim() == 3 and pw.shape[0] == 7 and pw.shape[2] == 32,
+             "packed weights must be a contiguous half [7, C_out, 32] on %s" % x.device)
+    c_out = int(pw.shape[1])
+    _require(pw.data_ptr() % 16 == 0, "packed weights must be 16-byte aligned")
+    _bias_ok(packed.bias, "bias", c_out, x.device)
+    _require(c_out > 0 and c_out % 32 == 0, "C_out must be a multiple of 32, got %d" % c_out)
+    _require(h * w * max(c_out, 3) < 2 ** 31, "one image's planes must stay below 2^31 elements")
+    out = _out(out, (n, c_out, _half_out(h, 2), _half_out(w, 2)), x, ((x, "x"), (pw, "the weights"), (packed.bias, "the bias")))
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().dba_conv7x7s2_f16(_p(x), _STEM_DTYPES[x.dtype], _p(pw), _p(packed.bias), c_out, n, h, w,
+                                                 int(bool(relu)), _p(out), _lib.stream(x.device)), "dba_conv7x7s2_f16")
+    return out
+
+
+def strided_fusable(conv, x):
+    """the encoders' fuse_conv facts for one 3x3 nn.Conv2d on x: a contiguous half device tensor, stride 1 or 2 with zero
+    padding 1, a convolution that would answer in half, C_in % 32 == 0 and C_out % 32 == 0"""
+    return (_half_map(x) and _geometry(conv, 3, (1, 2)) and _answers_half(conv, x.device) and conv.in_channels % 32 == 0
+            and conv.out_channels % 32 == 0 and x.shape[1] == conv.in_channels
+            and x.shape[2] * x.shape[3] * max(conv.in_channels, conv.out_channels) < 2 ** 31)
+
+
+def down_fusable(conv1, down, x):
+    """strided_fusable for a stride-2 block's conv1 together with its downsample[0], a 1x1 stride-2 convolution of the same
+    channels that answers in half as well"""
+    return (strided_fusable(conv1, x) and conv1.stride == (2, 2) and _geometry(down, 1, (2,)) and _answers_half(down, x.device)
+            and down.in_channels == conv1.in_channels and down.out_channels == conv1.out_channels)
+
+
+def encoder_stem_fusable(conv, x):
+    """conv_fusable for the encoders' stem: 7x7, stride 2, zero padding 3, three input channels, C_out a multiple of 32; x
+    half, or float32 while autocast to half is on (the kernel rounds it as autocast's cast would)"""
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dim() == 4 and x.is_contiguous() and x.numel() > 0):
+        return False
+    if not (_geometry(conv, 7, (2,)) and _answers_half(conv, x.device) and conv.in_channels == 3 and conv.out_channels % 32 == 0
+            and x.shape[1] == 3):
+        return False
+    casts = x.dtype == torch.float32 and torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.float16
+    return (x.dtype == torch.float16 or casts) and x.shape[2] * x.shape[3] * max(conv.out_channels, 3) < 2 ** 31

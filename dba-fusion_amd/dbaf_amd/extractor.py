@@ -14,7 +14,20 @@ their convolutions in HIP launches (csrc/extractor.hip), and the two statements 
 Every statement of the reference yields a tensor of the input dtype (half under autocast); the kernels round to that dtype
 where a statement ends and compute in float32 in between.  One workgroup holds one plane in registers, so a plane has at
 most MAX_PLANE = 65536 elements; the modules send larger ones to the statements.  The convolutions are the modules' own
-nn.Conv2d calls (MIOpen).
+nn.Conv2d calls (MIOpen) unless fuse_conv is set.
+
+BasicEncoder.fuse_conv / ResidualBlock.fuse_conv (class attributes, default off: then nothing changes; the encoder's setter
+forwards to its blocks) send the convolutions of the fused route to dbaf_amd.conv, each piece on its own facts:
+  stem               conv7x7s2, its ReLU in the epilogue for norm_fn 'none'; a float32 image under autocast is read as it is
+  a block's conv1    stride 2: conv3x3s_down, conv1 and downsample[0] in one launch; stride 1: THE RULE below; the ReLU in
+                     the epilogue for norm_fn 'none'
+  a block's conv2    THE RULE, no ReLU (the tail kernel applies it)
+  the encoder's conv2   conv1x1
+THE RULE for a stride-1 3x3: conv.conv3x3 where conv.conv_fusable holds (C_out % 64 == 0: the 64 -> 64 and 128 -> 128
+convolutions, its 128-channel workgroups), else conv.conv3x3s where conv.strided_fusable holds (32 -> 32).  It reads the
+module and the tensor's metadata only, never n.  A piece whose condition fails makes its stock call where it always did.
+With the flag, under autocast or as a half module, a forward calls no stock convolution, packs float32 parameters to half
+once per parameter version (no per-call casts) and returns the same bytes on every call.
 
 forward takes the fused route for norm_fn 'instance' and 'none' when the tensors are contiguous device tensors of float16
 or float32, every convolution answers in the dtype the statement before it produced, and nothing asks for a gradient;
@@ -27,6 +40,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from . import conv as _conv
 
 MAX_PLANE = 65536
 _DTYPES = {torch.float32: _lib.DBA_F32, torch.float16: _lib.DBA_F16}
@@ -244,14 +258,35 @@ class ResidualBlock(nn.Module):
             x = self.downsample(x)
         return self.relu(x + y)
 
+    fuse_conv = False    # conv1 (with downsample[0] at stride 2) and conv2 through dbaf_amd.conv where its conditions hold
+
+    def _routed(self, conv, x, relu):
+        """conv(x) under fuse_conv by the module docstring's RULE (through the ReLU when relu), or None: not routed"""
+        if _conv.conv_fusable(conv, x):
+            return _conv.conv3x3(x, _conv.pack_weights(conv), relu=relu)
+        if _conv.strided_fusable(conv, x):
+            return _conv.conv3x3s(x, _conv.pack_strided(conv), stride=conv.stride[0], relu=relu)
+        return None
+
     def _fused(self, x):
         """the fused chain, or None as soon as a tensor is not what the kernels take (nothing of the caller's is written)"""
         instance = self.norm_fn == "instance"
-        y = self.conv1(x)
-        if not _maps_ok(y) or y.dtype != x.dtype:
-            return None
-        y = _norm_unchecked(y, True, y, self.norm1.eps) if instance else y.relu_()
-        y = self.conv2(y)
+        y = d = None
+        if self.fuse_conv:
+            if self.downsample is not None and _conv.down_fusable(self.conv1, self.downsample[0], x):
+                y, d = _conv.conv3x3s_down(x, _conv.pack_down(self.conv1, self.downsample[0]), relu=not instance)
+            else:
+                y = self._routed(self.conv1, x, not instance)
+        if y is None:
+            y = self.conv1(x)
+            if not _maps_ok(y) or y.dtype != x.dtype:
+                return None
+            if not instance:
+                y = y.relu_()
+        if instance:
+            y = _norm_unchecked(y, True, y, self.norm1.eps)
+        z = self._routed(self.conv2, y, False) if self.fuse_conv else None
+        y = self.conv2(y) if z is None else z
         if not _maps_ok(y) or y.dtype != x.dtype:
             return None
         # y is this call's own tensor: it shares no byte with x or d, and out = y is the allowed in-place form
@@ -259,7 +294,8 @@ class ResidualBlock(nn.Module):
             if x.shape != y.shape:
                 return None
             return _norm_skip_unchecked(y, x, None, y, self.norm2.eps) if instance else _relu_skip_unchecked(y, x, y)
-        d = self.downsample[0](x)
+        if d is None:
+            d = self.downsample[0](x)
         if not _maps_ok(d) or d.dtype != y.dtype or d.shape != y.shape:
             return None
         return _norm_skip_unchecked(y, None, d, y, self.norm2.eps) if instance else _relu_skip_unchecked(y, d, y)
@@ -343,16 +379,40 @@ class BasicEncoder(nn.Module):
             return False
         return _no_grad_asked(self, x)
 
+    # the convolutions on the matrix cores (dbaf_amd.conv): the stem, the blocks' (forwarded to them) and conv2
+    @property
+    def fuse_conv(self):
+        return self.__dict__.get("_fuse_conv", False)
+
+    @fuse_conv.setter
+    def fuse_conv(self, on):
+        self.__dict__["_fuse_conv"] = bool(on)
+        for m in self.modules():
+            if isinstance(m, ResidualBlock):
+                m.fuse_conv = bool(on)
+
     def forward(self, x):
         if not self._fusable(x):
             return self.forward_statements(x)
         b, n, c1, h1, w1 = x.shape
-        y = self.conv1(x.view(b * n, c1, h1, w1))
-        if not _maps_ok(y):
-            return self.forward_statements(x)
-        y = _norm_unchecked(y, True, y, self.norm1.eps) if self.norm_fn == "instance" else y.relu_()
+        fuse, none = self.fuse_conv, self.norm_fn != "instance"
+        x4 = x.view(b * n, c1, h1, w1)
+        if fuse and _conv.encoder_stem_fusable(self.conv1, x4):
+            y = _conv.conv7x7s2(x4, _conv.pack_encoder_stem(self.conv1), relu=none)
+            if not _maps_ok(y):
+                return self.forward_statements(x)
+            if not none:
+                y = _norm_unchecked(y, True, y, self.norm1.eps)
+        else:
+            y = self.conv1(x4)
+            if not _maps_ok(y):
+                return self.forward_statements(x)
+            y = _norm_unchecked(y, True, y, self.norm1.eps) if self.norm_fn == "instance" else y.relu_()
         for blk in self._trunk():
             y = blk(y)
-        y = self.conv2(y)
+        if fuse and _conv.pointwise_fusable(self.conv2, y):
+            y = _conv.conv1x1(y, _conv.pack_pointwise(self.conv2))
+        else:
+            y = self.conv2(y)
         _, c2, h2, w2 = y.shape
         return y.view(b, n, c2, h2, w2)

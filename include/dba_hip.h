@@ -1049,6 +1049,43 @@ int dba_conv7x7_tile(void);
 int dba_conv7x7_f16(const void *x, int dtype, const void *weight, const void *bias, int c_out, int n, int h, int w, int relu,
                     void *out, dba_stream_t stream);
 
+/* ---- The encoders' convolutions on the matrix cores (csrc/conv_enc.hip) ------------------------------------------------
+ * The 16 convolutions of BasicEncoder (dbaf/modules/extractor.py:10-11, :45, :136, :145) that conv3x3 / conv1x1 above do not take:
+ * stride 2, C_out = 32, three input channels.  Half tensors [n, C, h, w]; implicit GEMM on mfma_f32_16x16x32_f16, float32
+ * accumulation in one fixed order (no atomics: the same bits on every run), then c = half(acc + float(bias)), ONE rounding;
+ * relu != 0: torch.relu(c) (NaN stays, -0 -> +0).  Positions outside the image are zeros and are never dereferenced.  The
+ * output has oh = (h - 1) / stride + 1 rows and ow = (w - 1) / stride + 1 columns.
+ * dba_conv3x3s_f16: nn.Conv2d(c_in, c_out, 3, stride=stride, padding=1)(x) (ResidualBlock.conv1 / conv2, extractor.py:10-11),
+ *   stride 1 or 2, c_in % 32 == 0, c_out % 32 == 0.  weight [9][c_out][c_in] half, tap-major (tap = 3 ky + kx), 16-byte
+ *   aligned; bias [c_out] half or NULL.  Order of an output element: chunks of 32 input channels ascending; inside a chunk
+ *   kx = 0, 1, 2; inside kx ky = 0, 1, 2; inside an MFMA the hardware's order.  It does not depend on n, on the tile, or on
+ *   how a workgroup's waves divide channels and rows (64 channels a workgroup where c_out % 64 == 0, else 32).
+ * dba_conv3x3s_down_f16: a stride-2 block's conv1 and its downsample[0] = nn.Conv2d(c_in, c_out, 1, stride=2) (extractor.py:
+ *   45) in one launch: downsample[0] reads input pixel (2y, 2x), the centre tap of conv1 at stride 2 with padding 1.
+ *   weight [10][c_out][c_in]: conv1's nine slices, then the 1x1 weight [c_out][c_in].  out = dba_conv3x3s_f16's bytes at
+ *   stride 2 (through the ReLU when relu != 0); out_down = half(sum_i Wd[o, i] * x[n, i, 2y, 2x] + float(bias_down[o])),
+ *   chunks ascending, never through the ReLU.  Both [n, c_out, oh, ow].
+ * dba_conv7x7s2_f16: the stem nn.Conv2d(3, c_out, 7, stride=2, padding=3)(x.half()) (extractor.py:136), c_out % 32 == 0.
+ *   x [n, 3, h, w], dtype DBA_F16 or DBA_F32, aligned to an element; a float32 value is rounded to half as it is read (to
+ *   nearest even, beyond 65504 to infinity): the bytes of x.to(torch.float16).  weight [7][c_out][32] half, entry [ky][o][4 kx
+ *   + i] = W[o, i, ky, kx] for kx < 7 and i < 3, ZERO for kx = 7 and for i = 3, 16-byte aligned.  The kernel feeds the
+ *   matrix core zeros in those slots too, so a NaN or an infinity of the input reaches exactly the outputs whose window
+ *   holds it.  Order of an output element: kernel rows ky = 0 .. 6 ascending, the hardware's order inside an MFMA.
+ * Refused without a launch, DBA_ERR_ARG: an extent <= 0, a stride other than 1 and 2, c_in % 32 or c_out % 32 not 0, a dtype
+ * other than the two, a null pointer (a bias excepted), a misaligned pointer, h * w * channels of one image or the grid
+ * beyond 2^31 - 1, an output that shares a byte with an input or with the other output.
+ * dba_conv3x3s_tile_rows(stride) / dba_conv3x3s_tile_cols(): a workgroup's tile of OUTPUT pixels (16 x 16 at stride 1, 8 rows
+ * x 16 columns at stride 2; 0 rows for another stride).  dba_conv7x7s2_tile: the side of the stem's square output tile. */
+int dba_conv3x3s_tile_rows(int stride);
+int dba_conv3x3s_tile_cols(void);
+int dba_conv7x7s2_tile(void);
+int dba_conv3x3s_f16(const void *x, const void *weight, const void *bias, int c_in, int c_out, int n, int h, int w, int stride,
+                     int relu, void *out, dba_stream_t stream);
+int dba_conv3x3s_down_f16(const void *x, const void *weight, const void *bias, const void *bias_down, int c_in, int c_out, int n,
+                          int h, int w, int relu, void *out, void *out_down, dba_stream_t stream);
+int dba_conv7x7s2_f16(const void *x, int dtype, const void *weight, const void *bias, int c_out, int n, int h, int w, int relu,
+                      void *out, dba_stream_t stream);
+
 /* ---- Encoder glue (csrc/extractor.hip) -----------------------------------------------------------------------------
  * What the feature and context encoders (dbaf/modules/extractor.py:47-55, :183-198) and their caller
  * (dbaf/motion_filter.py:29-30, :35-36, :64-65) run between the convolutions, which stay with the caller.  Tensors are
