@@ -55,6 +55,7 @@ struct UpdHead {
   float *sum;
   int k, relu_in, act;
   float scale;
+  int out_f32;   // out is float32 whatever T: the activation's float32 value, not rounded
 };
 
 struct UpdHeads {
@@ -92,6 +93,14 @@ __device__ __forceinline__ float upd_epilogue(float v, int act, float scale) {
   return v;
 }
 
+// the head's value for a float32 `out` (autocast's softplus on a half convolution): v is already h(s + b); the activation and
+// the scale stay in float32, nothing rounds behind them
+__device__ __forceinline__ float upd_epilogue_f32(float v, int act, float scale) {
+  if (act == DBA_UPD_ACT_SIGMOID) return 1.0f / (1.0f + expf(-v));
+  if (act == DBA_UPD_ACT_SOFTPLUS) return upd_f32(scale * upd_f32(v > 20.0f ? v : log1pf(expf(v))));
+  return v;
+}
+
 template <typename T, int K, bool VEC>
 __global__ __launch_bounds__(UPD_THREADS) void upd_heads_kernel(UpdHeads hs, int n, int c, int ht, int wd, unsigned tiles_x,
                                                                 unsigned tiles) {
@@ -114,6 +123,7 @@ __global__ __launch_bounds__(UPD_THREADS) void upd_heads_kernel(UpdHeads hs, int
   const int relu_in = second ? hs.h[1].relu_in : hs.h[0].relu_in;
   const int act = second ? hs.h[1].act : hs.h[0].act;
   const float scale = second ? hs.h[1].scale : hs.h[0].scale;
+  const int out_f32 = second ? hs.h[1].out_f32 : hs.h[0].out_f32;
 
   const unsigned e = local / tiles, tile = local - e * tiles;
   const int ty = (int)(tile / tiles_x), tx = (int)(tile - (unsigned)ty * tiles_x);
@@ -289,6 +299,16 @@ __global__ __launch_bounds__(UPD_THREADS) void upd_heads_kernel(UpdHeads hs, int
     }
     s0 = upd_f32(s0 + b0);
     s1 = upd_f32(s1 + b1);
+    if (out_f32) {   // uniform over the workgroup
+      float *of = (float *)out;
+      of[(long long)k * pix] = upd_epilogue_f32(upd_rnd<T>(s0), act, scale);
+      if (k == 2) of[2 * pix + 1] = upd_epilogue_f32(upd_rnd<T>(s1), act, scale);
+      if (sum) {
+        sum[(long long)k * pix] = s0;
+        if (k == 2) sum[2 * pix + 1] = s1;
+      }
+      continue;
+    }
     const T o0 = (T)upd_epilogue<T>(upd_rnd<T>(s0), act, scale);
     if (k == 2) {
       const T o1 = (T)upd_epilogue<T>(upd_rnd<T>(s1), act, scale);
@@ -357,16 +377,17 @@ int dba_upd_heads(const dba_upd_head_t *heads, int n_heads, int n, int c, int ht
     const dba_upd_head_t &h = heads[i];
     if (!h.x || !h.weight || !h.out || (h.k != 1 && h.k != 2)) return DBA_ERR_ARG;
     if (h.act != DBA_UPD_ACT_NONE && h.act != DBA_UPD_ACT_SIGMOID && h.act != DBA_UPD_ACT_SOFTPLUS) return DBA_ERR_ARG;
-    if (((uintptr_t)h.x | (uintptr_t)h.weight | (uintptr_t)h.bias | (uintptr_t)h.out) % isz || (uintptr_t)h.sum % 4)
+    if (((uintptr_t)h.x | (uintptr_t)h.weight | (uintptr_t)h.bias) % isz || (uintptr_t)h.out % (h.out_f32 ? 4 : isz) ||
+        (uintptr_t)h.sum % 4)
       return DBA_ERR_ARG;
-    hs.h[i] = UpdHead{h.x, h.weight, h.bias, h.out, h.sum, h.k, h.relu_in != 0, h.act, h.scale};
+    hs.h[i] = UpdHead{h.x, h.weight, h.bias, h.out, h.sum, h.k, h.relu_in != 0, h.act, h.scale, h.out_f32 != 0};
     vec = vec && ((uintptr_t)h.x & 15) == 0;
     kmax = h.k > kmax ? h.k : kmax;
   }
   // what a head writes shares no byte with anything the call reads, nor with what else it writes
   for (int i = 0; i < n_heads; i++) {
     const dba_upd_head_t &h = heads[i];
-    const long long obytes = (long long)n * hw * h.k * isz, sbytes = (long long)n * hw * h.k * 4;
+    const long long obytes = (long long)n * hw * h.k * (h.out_f32 ? 4 : isz), sbytes = (long long)n * hw * h.k * 4;
     if (ranges_overlap(h.out, obytes, h.sum, sbytes)) return DBA_ERR_ARG;
     for (int j = 0; j < n_heads; j++) {
       const dba_upd_head_t &g = heads[j];
@@ -377,7 +398,7 @@ int dba_upd_heads(const dba_upd_head_t *heads, int n_heads, int n, int c, int ht
         if (ranges_overlap(p, pbytes, g.x, xbytes) || ranges_overlap(p, pbytes, g.weight, wbytes) ||
             ranges_overlap(p, pbytes, g.bias, bbytes))
           return DBA_ERR_ARG;
-        if (j != i && (ranges_overlap(p, pbytes, g.out, (long long)n * hw * g.k * isz) ||
+        if (j != i && (ranges_overlap(p, pbytes, g.out, (long long)n * hw * g.k * (g.out_f32 ? 4 : isz)) ||
                        ranges_overlap(p, pbytes, g.sum, (long long)n * hw * g.k * 4)))
           return DBA_ERR_ARG;
       }

@@ -52,7 +52,7 @@ class AfGeometry(ctypes.Structure):
 class UpdHead(ctypes.Structure):
     """dba_upd_head_t of include/dba_hip.h"""
     _fields_ = [("x", c_void_p), ("weight", c_void_p), ("bias", c_void_p), ("out", c_void_p), ("sum", c_void_p),
-                ("k", c_int), ("relu_in", c_int), ("act", c_int), ("scale", c_float)]
+                ("k", c_int), ("relu_in", c_int), ("act", c_int), ("scale", c_float), ("out_f32", c_int)]
 
 
 class FrameItem(ctypes.Structure):

@@ -46,6 +46,13 @@ fuse_flow_stem (default off: then nothing changes; independent of fuse_conv) rou
 dbaf_amd.conv.conv7x7: ONE launch in place of the stem on MIOpen, the in-place ReLU behind it and, where the caller hands a
 float32 flow under autocast (CorrBlock.lookup_motion does), autocast's cast in front of it -- the kernel rounds the float32
 values to half as it reads them.  With both switches a forward with upsample=False makes no stock convolution call.
+
+fuse_agg (default off: then nothing changes; GraphAgg's switch, UpdateModule.fuse_agg forwards to it; independent of the three
+others) finishes upsample mode: conv1 / conv2 with their ReLUs go through conv3x3 as under fuse_conv; under autocast, eta is
+ONE heads launch with Head.out_dtype = torch.float32 (v = s + b rounded once to half, softplus and the factor .01 in float32,
+the dtype the statements return); the 128 -> 576 mask convolution is conv1x1 wherever forward called self.upmask(net), and
+an UpmaskSource made under the switch materializes through conv1x1 too.  With fuse_conv and fuse_flow_stem as well, a forward
+with upsample=True makes no stock convolution call, under autocast or not.  Each piece routes on its own facts.
 """
 import ctypes
 
@@ -74,11 +81,13 @@ def _overlap(x, y):
 class Head:
     """one head of a heads() call.  x [n, c, ht, wd]; weight [k, c, 3, 3], k in {1, 2}; bias [k] or None; relu_in: x is
     still before its ReLU; act: "none" | "sigmoid" | "softplus" (then out = scale * softplus(v), rounded after each);
-    out: where to write [n, ht, wd, k] (default: a new tensor); want_sum: also return the float32 s + b"""
+    out: where to write [n, ht, wd, k] (default: a new tensor); want_sum: also return the float32 s + b; out_dtype: None
+    (x's dtype) or torch.float32 -- then v = s + b is still rounded ONCE to x's dtype, and the activation and the scale
+    behind it stay in float32, unrounded: what autocast's float32 softplus makes of a half convolution"""
 
-    def __init__(self, x, weight, bias=None, relu_in=False, act="none", scale=1.0, out=None, want_sum=False):
+    def __init__(self, x, weight, bias=None, relu_in=False, act="none", scale=1.0, out=None, want_sum=False, out_dtype=None):
         self.x, self.weight, self.bias, self.relu_in, self.act, self.scale = x, weight, bias, bool(relu_in), act, float(scale)
-        self.out, self.want_sum = out, bool(want_sum)
+        self.out, self.want_sum, self.out_dtype = out, bool(want_sum), out_dtype
 
 
 def tile():
@@ -114,17 +123,21 @@ def heads(*specs):
                  "%s.weight must be [1 or 2, %d, 3, 3], got %s" % (nm, c, tuple(h.weight.shape)))
         k = int(h.weight.shape[0])
         _require(h.bias is None or tuple(h.bias.shape) == (k,), "%s.bias must be [%d]" % (nm, k))
+        _require(h.out_dtype in (None, x0.dtype, torch.float32), "%s.out_dtype must be None, %s or torch.float32, got %r"
+                 % (nm, x0.dtype, h.out_dtype))
+        odt = x0.dtype if h.out_dtype is None else h.out_dtype
         if h.out is None:
-            out = torch.empty((n, ht, wd, k), dtype=x0.dtype, device=x0.device)
+            out = torch.empty((n, ht, wd, k), dtype=odt, device=x0.device)
         else:
             out = h.out
-            _require(isinstance(out, torch.Tensor) and out.is_cuda and out.device == x0.device and out.dtype == x0.dtype
+            _require(isinstance(out, torch.Tensor) and out.is_cuda and out.device == x0.device and out.dtype == odt
                      and out.is_contiguous() and tuple(out.shape) == (n, ht, wd, k),
-                     "%s.out must be a contiguous [%d, %d, %d, %d] of %s on %s" % (nm, n, ht, wd, k, x0.dtype, x0.device))
+                     "%s.out must be a contiguous [%d, %d, %d, %d] of %s on %s" % (nm, n, ht, wd, k, odt, x0.device))
         s = torch.empty((n, ht, wd, k), dtype=torch.float32, device=x0.device) if h.want_sum else None
         written.append((out, nm + ".out"))
         arr[i] = _lib.UpdHead(h.x.data_ptr(), h.weight.data_ptr(), h.bias.data_ptr() if h.bias is not None else None,
-                              out.data_ptr(), s.data_ptr() if s is not None else None, k, int(h.relu_in), ACTS[h.act], h.scale)
+                              out.data_ptr(), s.data_ptr() if s is not None else None, k, int(h.relu_in), ACTS[h.act], h.scale,
+                              int(odt != x0.dtype))
         results.append((out, s) if h.want_sum else out)
     for i, (o, onm) in enumerate(written):
         for t, tnm in read:
@@ -266,6 +279,8 @@ class GraphAgg(nn.Module):
     last_uniq: the frames of the last forward, ascending (what torch.unique(ii) gives), for the caller's statements."""
     fuse_upmask = False
     fuse_conv = False    # conv1 / conv2 with their ReLUs through dbaf_amd.conv.conv3x3 where its conditions hold
+    fuse_agg = False     # conv1 / conv2 as under fuse_conv, eta under autocast in one launch, the mask convolution as conv1x1
+                         # (module docstring); independent of the three other switches
     plan_rows = None     # None: the most the plan kernel covers
     last_uniq = None
 
@@ -301,9 +316,17 @@ class GraphAgg(nn.Module):
         return self._conv_relu(self.conv2, net, plain), batch, ht, wd
 
     def _conv_relu(self, conv, x, plain):
-        if not plain and self.fuse_conv and _conv.conv_fusable(conv, x) and not _asks_gradient(self, (x,)):
+        if (not plain and (self.fuse_conv or self.fuse_agg) and _conv.conv_fusable(conv, x)
+                and not _asks_gradient(self, (x,))):
             return _conv.conv3x3(x, _conv.pack_weights(conv), relu=True)
         return self.relu(conv(x))
+
+    def _mask(self, net, batch, ht, wd):
+        """the mask's 1x1 convolution as a tensor: under fuse_agg one conv1x1 launch (576 = 9 * 64 outputs) where its facts
+        hold, else the stock convolution"""
+        if self.fuse_agg and _conv.pointwise_fusable(self.upmask[0], net) and not _asks_gradient(self, (net,)):
+            return _conv.conv1x1(net, _conv.pack_pointwise(self.upmask[0])).view(batch, -1, 8 * 8 * 9, ht, wd)
+        return self.upmask(net).view(batch, -1, 8 * 8 * 9, ht, wd)
 
     def forward_statements(self, net, ii):
         """the reference's chain in plain torch ops, on any device"""
@@ -327,16 +350,20 @@ class GraphAgg(nn.Module):
         net, batch, ht, wd = self._aggregate(net, ii, False)
         # conv2's ReLU stays a torch launch (upmask's convolution reads it too), so eta reads it with relu_in off.
         # Under autocast torch's softplus answers in float32: then the statements run.
+        # Under fuse_agg and a half state the kernel answers in float32 as they do (Head.out_dtype): v rounded once to half,
+        # softplus and the factor in float32.
         if _head_fusable(self, self.eta[0], net) and not torch.is_autocast_enabled():
             w, b = _params(self.eta[0], net.dtype)
             eta = heads(Head(net, w, b, relu_in=False, act="softplus", scale=.01))[0].view(batch, -1, ht, wd)
+        elif self.fuse_agg and net.dtype == torch.float16 and _head_fusable(self, self.eta[0], net):
+            w, b = _params(self.eta[0], net.dtype)
+            eta = heads(Head(net, w, b, relu_in=False, act="softplus", scale=.01, out_dtype=torch.float32))[0].view(batch, -1, ht, wd)
         else:
             eta = .01 * self.eta(net).view(batch, -1, ht, wd)
         if self._upmask_fusable(net):
             w, b = _params(self.upmask[0], net.dtype)
-            return eta, UpmaskSource(net, w, b, uniq=self.last_uniq, batch=batch)
-        upmask = self.upmask(net).view(batch, -1, 8 * 8 * 9, ht, wd)
-        return eta, upmask
+            return eta, UpmaskSource(net, w, b, uniq=self.last_uniq, batch=batch, matrix_cores=self.fuse_agg)
+        return eta, self._mask(net, batch, ht, wd)
 
 
 class UpdateModule(nn.Module):
@@ -362,6 +389,15 @@ class UpdateModule(nn.Module):
     @fuse_upmask.setter
     def fuse_upmask(self, on):
         self.agg.fuse_upmask = bool(on)
+
+    # GraphAgg's own switch under the operator's name: the aggregation, eta under autocast and the mask on this project's kernels
+    @property
+    def fuse_agg(self):
+        return self.agg.fuse_agg
+
+    @fuse_agg.setter
+    def fuse_agg(self, on):
+        self.agg.fuse_agg = bool(on)
 
     # flow_encoder[0] with its ReLU as ONE dbaf_amd.conv.conv7x7 launch where stem_fusable holds; a switch of its own,
     # independent of fuse_conv

@@ -78,9 +78,10 @@ class UpmaskSource:
       weight  [576, 128] (or [576, 128, 1, 1]) float16, bias [576] float16 or None
       uniq    [B] int64: the frames of the plan (None when the source was not made by a module)
       batch   the leading dimension of the tensor it stands for, [batch, B / batch, 576, ht, wd]
+      matrix_cores  materialize() runs dbaf_amd.conv.conv1x1 (a source made under GraphAgg.fuse_agg) in place of the stock call
     Checked here, so that a source that exists can be launched.  materialize() runs the stock convolution."""
 
-    def __init__(self, x, weight, bias=None, uniq=None, batch=1):
+    def __init__(self, x, weight, bias=None, uniq=None, batch=1, matrix_cores=False):
         for t, nm in ((x, "x"), (weight, "weight")) + (((bias, "bias"),) if bias is not None else ()):
             _require(isinstance(t, torch.Tensor) and t.is_cuda, "UpmaskSource.%s must be a HIP device tensor; no CPU path" % nm)
             _require(t.dtype == torch.float16, "UpmaskSource.%s must be float16 (the fused launch is half only), got %s" % (nm, t.dtype))
@@ -92,6 +93,7 @@ class UpmaskSource:
         _require(bias is None or tuple(bias.shape) == (576,), "UpmaskSource.bias must be [576]")
         _require(int(batch) > 0 and x.shape[0] % int(batch) == 0, "UpmaskSource.batch must divide x's %d frames" % x.shape[0])
         self.x, self.weight, self.bias, self.uniq, self.batch = x, weight, bias, uniq, int(batch)
+        self.matrix_cores = bool(matrix_cores)
 
     @property
     def shape(self):
@@ -107,6 +109,9 @@ class UpmaskSource:
     def materialize(self):
         """the tensor the stock convolution gives, [batch, B / batch, 576, ht, wd]"""
         b = self.bias
+        if self.matrix_cores:
+            from . import conv   # [576, 128] with 128 a multiple of 32 is pack_pointwise's layout already
+            return conv.conv1x1(self.x, conv.Pointwise(self.weight.view(576, 128), b, 128)).view(self.shape)
         return torch.nn.functional.conv2d(self.x, self.weight.view(576, 128, 1, 1), b).view(self.shape)
 
 

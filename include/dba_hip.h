@@ -1154,6 +1154,9 @@ typedef struct {
   int relu_in;        /* apply ReLU to x as it is read */
   int act;            /* DBA_UPD_ACT_NONE | _SIGMOID | _SOFTPLUS */
   float scale;        /* _SOFTPLUS only: out = h(scale * h(softplus(v))) */
+  int out_f32;        /* != 0: out is float32 [n, ht, wd, k] whatever the dtype (autocast's softplus answers so): v = h(s + b)
+                         as before, then the activation in float32 with NO rounding behind it: v | 1 / (1 + expf(-v)) |
+                         scale * softplus(v) */
 } dba_upd_head_t;
 int dba_upd_heads(const dba_upd_head_t *heads, int n_heads, int n, int c, int ht, int wd, int dtype, dba_stream_t stream);
 int dba_upd_heads_tile(int *rows, int *cols); /* the kernel's tile extents, for the tests */
