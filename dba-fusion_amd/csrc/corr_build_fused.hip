@@ -1647,14 +1647,78 @@ __global__ void fmap_pixel_major_pair_kernel(const _Float16 *in1, _Float16 *out1
 
 using namespace dba;
 
+namespace {
+
+// The environment switches of the build, each read once per process (A/B runs and the tests of the older forms)
+struct BuildEnv {
+  int force;        // DBA_BUILD_KERNEL=classic|loop forces one form where both apply: 0 automatic, 1 classic, 2 loop
+  int native_mode;  // DBA_BUILD_OPERANDS=copy|bnative: 0 copies of both maps, 1 both maps as they lie, 2 the target map only
+  bool waves16;     // DBA_BUILD_WAVES=8 keeps the eight-wave forms
+  bool g16_generic; // DBA_BUILD_G16_GENERIC=1: 55 columns on the generic instantiation
+};
+const BuildEnv &build_env() {
+  static const BuildEnv env = [] {
+    BuildEnv v;
+    const char *e = getenv("DBA_BUILD_KERNEL");
+    v.force = !e ? 0 : (e[0] == 'c' ? 1 : (e[0] == 'l' ? 2 : 0));
+    e = getenv("DBA_BUILD_OPERANDS");
+    v.native_mode = !e ? 1 : (e[0] == 'c' ? 0 : (e[0] == 'b' ? 2 : 1));
+    e = getenv("DBA_BUILD_WAVES");
+    v.waves16 = !(e && atoi(e) == 8);
+    v.g16_generic = getenv("DBA_BUILD_G16_GENERIC") != nullptr;
+    return v;
+  }();
+  return env;
+}
+
+// Which kernel a SUPPORTED shape gets: the one place the launch conditions live (dba_corr_volume_build_route reports it, the
+// launcher switches on it).  tiled / padded: the planes' pixel order (shear_grid) and whether the grid is larger than the map.
+int corr_build_route(int C, int h1, int w1, int h2, int w2, bool tiled, bool padded, const BuildEnv &env) {
+  const int HW1 = h1 * w1, HW2 = h2 * w2;
+  // the strip walk for every map up to 64 wide at C = 128 (since the row-end quads are stored by the whole wave it also
+  // wins where strips span row ends: 55x55 13.3 against 14.3 us/edge)
+  const bool loop_form = (w2 <= 64 && C == 128 && env.force != 1);
+  // sixteen waves per workgroup on planes in the linear pixel order: the general form, on the k-block-major copies
+  // (where 16-byte pieces of the maps are aligned -- widths that are multiples of 8 -- the eight-wave walk on the caller's own maps
+  // is as fast or faster: 40 x 56 6.1 against 6.2 us per edge, 30 x 40 2.6 against 2.8; profiles/r06_build_g16.txt)
+  const bool general16 = loop_form && env.waves16 && !tiled && w2 > 32 && h1 == h2 && w1 == w2 && ((w2 % 8) != 0 || (HW2 % 8) != 0);
+  // ... and, where 8-byte pieces of the maps are aligned, straight from the caller's [n][C][h][w] maps
+  const bool native_b = loop_form && !general16 && !padded && env.native_mode != 0 && (w2 % 8 == 0) && (HW2 % 8 == 0);
+  const bool native = native_b && env.native_mode == 1 && (HW1 % 8 == 0) && (w1 % 8 == 0);
+  if (loop_form) {
+    // 55 x 55 (the reference's TUM-VI demo, demo_vio_tumvi.py:55-60) has its own instantiation
+    if (general16) return (w2 == 55 && !env.g16_generic) ? DBA_CORR_ROUTE_FUSED16G_55 : DBA_CORR_ROUTE_FUSED16G;
+    if (native && tiled && w2 == 64 && (h2 % 8) == 0 && env.waves16) return DBA_CORR_ROUTE_FUSED16;   // the shapes the headline runs on
+    if (native) return DBA_CORR_ROUTE_WALK_NATIVE;
+    if (native_b) return DBA_CORR_ROUTE_WALK_NATIVE_B;
+    return DBA_CORR_ROUTE_WALK_COPY;
+  }
+  if (w2 <= 64) return DBA_CORR_ROUTE_STRIP_64;
+  // sixteen waves per workgroup where the planes keep the linear pixel order
+  if (env.waves16 && !tiled && h1 == h2 && w1 == w2 && (C % 16) == 0 && C <= 512) return DBA_CORR_ROUTE_FUSED16W;
+  return DBA_CORR_ROUTE_STRIP_128;
+}
+
+}  // namespace
+
 extern "C" {
 
 int dba_corr_volume_build_sheared_supported(int C, int h1, int w1, int h2, int w2, int num_levels) {
   if (C <= 0 || (C % 16) != 0 || num_levels != 4 || h1 <= 0 || w1 <= 0) return 0;
   if (w2 > 128 || (h2 >> 3) < 1 || (w2 >> 3) < 1) return 0;
   if (C > 512) return 0;  // the strip's source operand (64 x C halves) is staged inside the level-0 tile
+  // dy = ty - (y1 >> l) and tx = (x1 >> l) + dx take ONE conditional wrap in every kernel: a source map more than one row or
+  // column larger than the target map would be stored at wrapped offsets ("Correlation build: the statement")
+  if (h1 > h2 + 1 || w1 > w2 + 1) return 0;
   const size_t elems0 = (size_t)h2 * w2 * (size_t)dba_corr_sheared_plane_elems(h1, w1);
   return (2 * elems0 < ((size_t)1 << 31)) ? 1 : 0;  // one edge-level is addressed through a 31-bit buffer range
+}
+
+int dba_corr_volume_build_route(int C, int h1, int w1, int h2, int w2, int num_levels) {
+  if (!dba_corr_volume_build_sheared_supported(C, h1, w1, h2, w2, num_levels)) return DBA_CORR_ROUTE_UNFUSED;
+  int h1g, w1g;
+  const bool tiled = shear_grid(h1, w1, &h1g, &w1g);
+  return corr_build_route(C, h1, w1, h2, w2, tiled, tiled && (h1g != h1 || w1g != w1), build_env());
 }
 
 int dba_corr_volume_build_sheared(const void *fmap1, const void *fmap2, void *const *sheared_levels, int n, int C,
@@ -1684,28 +1748,14 @@ int dba_corr_volume_build_sheared_slots(const void *fmap1, const void *fmap2, vo
   const int tiled = shear_grid(h1, w1, &h1g, &w1g) ? 1 : 0;
   const bool padded = tiled && (h1g != h1 || w1g != w1);
   const int h1k = tiled ? h1g : h1, w1k = tiled ? w1g : w1;
-  // DBA_BUILD_KERNEL=classic|loop forces one form where both apply (tests, A/B runs); read once per process
-  static const int force = [] {
-    const char *e = getenv("DBA_BUILD_KERNEL");
-    return !e ? 0 : (e[0] == 'c' ? 1 : (e[0] == 'l' ? 2 : 0));
-  }();
-  // the strip walk for every map up to 64 wide at C = 128 (since the row-end quads are stored by the whole wave it also
-  // wins where strips span row ends: 55x55 13.3 against 14.3 us/edge)
-  const bool loop_form = (w2 <= 64 && C == 128 && force != 1);
-  // ... and, where 8-byte pieces of the maps are aligned, straight from the caller's [n][C][h][w] maps
-  // (DBA_BUILD_OPERANDS=copy keeps the k-block-major copies: A/B runs)
-  static const int native_mode = [] {   // 0: copies of both maps, 1: both maps as they lie, 2: the target map only
-    const char *e = getenv("DBA_BUILD_OPERANDS");
-    return !e ? 1 : (e[0] == 'c' ? 0 : (e[0] == 'b' ? 2 : 1));
-  }();
-  // sixteen waves per workgroup (DBA_BUILD_WAVES=8 keeps the eight-wave walks: A/B runs); on planes in the linear pixel order: the
-  // general form, on the k-block-major copies
-  static const bool waves16 = [] { const char *e = getenv("DBA_BUILD_WAVES"); return !(e && atoi(e) == 8); }();
-  // (where 16-byte pieces of the maps are aligned -- widths that are multiples of 8 -- the eight-wave walk on the caller's own maps
-  // is as fast or faster: 40 x 56 6.1 against 6.2 us per edge, 30 x 40 2.6 against 2.8; profiles/r06_build_g16.txt)
-  const bool general16 = loop_form && waves16 && !tiled && w2 > 32 && h1 == h2 && w1 == w2 && ((w2 % 8) != 0 || (HW2 % 8) != 0);
-  const bool native_b = loop_form && !general16 && !padded && native_mode != 0 && (w2 % 8 == 0) && (HW2 % 8 == 0);
-  const bool native = native_b && native_mode == 1 && (HW1 % 8 == 0) && (w1 % 8 == 0);
+  const BuildEnv &env = build_env();
+  const int force = env.force;
+  const int route = corr_build_route(C, h1, w1, h2, w2, tiled != 0, padded, env);
+  // what the route says about the operands and the walk (corr_build_route)
+  const bool general16 = route == DBA_CORR_ROUTE_FUSED16G || route == DBA_CORR_ROUTE_FUSED16G_55;
+  const bool native = route == DBA_CORR_ROUTE_FUSED16 || route == DBA_CORR_ROUTE_WALK_NATIVE;
+  const bool native_b = native || route == DBA_CORR_ROUTE_WALK_NATIVE_B;
+  const bool loop_form = general16 || native_b || route == DBA_CORR_ROUTE_WALK_COPY;
   const int HW1o = tiled ? HW1p : HW1;   // pixels per map of the source operand's copy
   if (!native && !native_b && HW1 == HW2 && 2 * (long long)n <= 65535)   // both copies in one launch
     hipLaunchKernelGGL(fmap_pixel_major_pair_kernel, dim3((HW1 + 63) / 64, (C + 63) / 64, 2 * n), dim3(256), 0, s,
@@ -1823,14 +1873,12 @@ int dba_corr_volume_build_sheared_slots(const void *fmap1, const void *fmap2, vo
                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         attr16g_once.done();
       }
-      // 55 x 55 (the reference's TUM-VI demo, demo_vio_tumvi.py:55-60) has its own instantiation (DBA_BUILD_G16_GENERIC=1: A/B runs)
-      static const bool g16_generic = getenv("DBA_BUILD_G16_GENERIC") != nullptr;
-      if (w2 == 55 && !g16_generic)
+      if (route == DBA_CORR_ROUTE_FUSED16G_55)
         hipLaunchKernelGGL(corr_build_fused16g_kernel<55>, lgrid, dim3(1024), lds16, s, A, Bm, L, h1, w1, h2, w2, HW1p, inv_w1, spw, out_slots F16_PROF_ARG);
       else
         hipLaunchKernelGGL(corr_build_fused16g_kernel<0>, lgrid, dim3(1024), lds16, s, A, Bm, L, h1, w1, h2, w2, HW1p, inv_w1, spw, out_slots F16_PROF_ARG);
       F16_PROF_DUMP();
-    } else if (native && tiled && w2 == 64 && (h2 % 8) == 0 && waves16) {   // the shapes the headline runs on
+    } else if (route == DBA_CORR_ROUTE_FUSED16) {
       static DeviceOnce attr16_once;
       if (attr16_once.needed()) {
         DBA_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&corr_build_fused16_kernel),
@@ -1840,25 +1888,25 @@ int dba_corr_volume_build_sheared_slots(const void *fmap1, const void *fmap2, vo
       hipLaunchKernelGGL(corr_build_fused16_kernel, lgrid, dim3(1024), lds16, s, static_cast<const _Float16 *>(fmap1),
                          static_cast<const _Float16 *>(fmap2), L, h1, w1, h2, HW1p, spw, out_slots F16_PROF_ARG);
       F16_PROF_DUMP();
-    } else if (native)
+    } else if (route == DBA_CORR_ROUTE_WALK_NATIVE)
       hipLaunchKernelGGL((corr_build_fused_kernel<2, true, true>), lgrid, dim3(512), lds, s, static_cast<const _Float16 *>(fmap1),
                          static_cast<const _Float16 *>(fmap2), L, C, h1k, w1k, h2, w2, HW1p, inv_w1, spw, out_slots,
                          tiled FB_PROF_ARG);
-    else if (native_b)
+    else if (route == DBA_CORR_ROUTE_WALK_NATIVE_B)
       hipLaunchKernelGGL((corr_build_fused_kernel<2, true, false, true>), lgrid, dim3(512), lds, s, A,
                          static_cast<const _Float16 *>(fmap2), L, C, h1k, w1k, h2, w2, HW1p, inv_w1, spw, out_slots,
                          tiled FB_PROF_ARG);
     else
       hipLaunchKernelGGL((corr_build_fused_kernel<2, true>), lgrid, dim3(512), lds, s, A, Bm, L, C, h1k, w1k, h2, w2, HW1p,
                          inv_w1, spw, out_slots, tiled FB_PROF_ARG);
-  } else if (w2 <= 64) {
+  } else if (route == DBA_CORR_ROUTE_STRIP_64) {
     const size_t lds = sizeof(_Float16) * (size_t)64 * (FT_ROWS * (64 + 4) + 4);  // the pooled levels live inside the dead tile
     hipLaunchKernelGGL((corr_build_fused_kernel<2, false>), grid, dim3(512), lds, s, A, Bm, L, C, h1k, w1k, h2, w2, HW1p, inv_w1,
                        1, out_slots, tiled FB_PROF_ARG);
   } else {
     const size_t lds = sizeof(_Float16) * (size_t)64 * (FT_ROWS * (128 + 4) + 4);
     // sixteen waves per workgroup where the planes keep the linear pixel order (DBA_BUILD_WAVES=8: the eight-wave form; A/B runs)
-    if (waves16 && !tiled && h1 == h2 && w1 == w2 && (C % 16) == 0 && C <= 512) {
+    if (route == DBA_CORR_ROUTE_FUSED16W) {
       static DeviceOnce attr16w_once;
       if (attr16w_once.needed()) {
         DBA_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&corr_build_fused16w_kernel),

@@ -122,6 +122,7 @@ SYMBOLS = {
     "dba_corr_index_forward": (c_int, [_P, _P, _P] + [c_int] * 7 + [_P]),
     "dba_corr_lookup_pyramid": (c_int, [_P, _P, _P] + [c_int] * 8 + [_P]),
     "dba_corr_volume_build_sheared_supported": (c_int, [c_int] * 6),
+    "dba_corr_volume_build_route": (c_int, [c_int] * 6),
     "dba_corr_volume_build_sheared": (c_int, [_P, _P, _P] + [c_int] * 7 + [_P, c_size_t, _P]),
     "dba_corr_sheared_plane_elems": (c_int, [c_int, c_int]),
     "dba_corr_sheared_tiled": (c_int, [c_int, c_int]),

@@ -410,8 +410,26 @@ int dba_corr_lookup_arm_timing(void *start_event, void *stop_event);
  * 2x2 pooling of the rounded levels and the flow-aligned store in one pass; every output byte is written once.
  * Supported when dba_corr_volume_build_sheared_supported(...) returns 1 (w2 <= 128, C % 16 == 0, 4 levels, every
  * level non-empty); sheared_levels[l] is [n, h2>>l, w2>>l, dba_corr_sheared_plane_elems(h1, w1)] f16.  scratch as for
- * dba_corr_volume_build. */
+ * dba_corr_volume_build.  Source and target maps may differ in size as long as every source row and column is a residue
+ * of the target map after ONE conditional wrap (h1 <= h2 + 1 and w1 <= w2 + 1: the kernels' dy and dx take a single
+ * correction); larger source maps are not supported. */
 int dba_corr_volume_build_sheared_supported(int C, int h1, int w1, int h2, int w2, int num_levels);
+/* Which kernel dba_corr_volume_build_sheared[_slots] launches for a shape: a pure host decision (the shape, the planes' pixel
+ * order and the DBA_BUILD_KERNEL / DBA_BUILD_OPERANDS / DBA_BUILD_WAVES / DBA_BUILD_G16_GENERIC switches, each read once per
+ * process); nothing is launched.  The launcher switches on the same value. */
+enum dba_corr_build_route {
+  DBA_CORR_ROUTE_UNFUSED = 0,       /* not supported: dba_corr_volume_build + dba_corr_shear_level */
+  DBA_CORR_ROUTE_FUSED16 = 1,       /* corr_build_fused16_kernel: sixteen waves, tiled planes, 64 columns, the maps as they lie */
+  DBA_CORR_ROUTE_FUSED16G = 2,      /* corr_build_fused16g_kernel<0>: sixteen waves, linear planes, 33..63 unaligned columns */
+  DBA_CORR_ROUTE_FUSED16G_55 = 3,   /* corr_build_fused16g_kernel<55> */
+  DBA_CORR_ROUTE_FUSED16W = 4,      /* corr_build_fused16w_kernel: sixteen waves, linear planes, 65..128 columns */
+  DBA_CORR_ROUTE_WALK_NATIVE = 5,   /* corr_build_fused_kernel<2, true, true>: strip walk, both maps as they lie */
+  DBA_CORR_ROUTE_WALK_NATIVE_B = 6, /* corr_build_fused_kernel<2, true, false, true>: strip walk, the target map as it lies */
+  DBA_CORR_ROUTE_WALK_COPY = 7,     /* corr_build_fused_kernel<2, true>: strip walk on the k-block-major copies */
+  DBA_CORR_ROUTE_STRIP_64 = 8,      /* corr_build_fused_kernel<2, false>: one strip per workgroup, up to 64 columns */
+  DBA_CORR_ROUTE_STRIP_128 = 9      /* corr_build_fused_kernel<4, false>: one strip per workgroup, 65..128 columns */
+};
+int dba_corr_volume_build_route(int C, int h1, int w1, int h2, int w2, int num_levels);
 int dba_corr_volume_build_sheared(const void *fmap1, const void *fmap2, void *const *sheared_levels, int n, int C,
                                   int h1, int w1, int h2, int w2, int num_levels, void *scratch,
                                   size_t scratch_bytes, dba_stream_t stream);
