@@ -54,6 +54,9 @@ struct BaEnv {
   bool fuse_update = !is("DBA_BA_FUSE_UPDATE", "0");   // see ba_run_loop
   // stage 0 of a keyed call: a workgroup of its first linearisation ("fold") or a launch of its own in front of it ("launch")
   bool stage0_fold = getenv("DBA_BA_STAGE0") ? is("DBA_BA_STAGE0", "fold") : STAGE0_FOLD_DEFAULT;
+  // the row-pair Schur form on its (row, partner slot) grid (ba_schur_kernel) instead of the pair list (ba_schur_pairs_kernel);
+  // dba_ba_schur_sparse_select changes it
+  int schur_sparse_legacy = is("DBA_SCHUR_SPARSE", "legacy");
 };
 static const BaEnv &ba_env() { static const BaEnv env; return env; }
 
@@ -64,6 +67,7 @@ static const BaEnv &ba_env() { static const BaEnv env; return env; }
 static std::atomic<int> g_schur_form{ba_env().schur_form};
 static std::atomic<int> g_deterministic{ba_env().deterministic};
 static std::atomic<int> g_solve_check{ba_env().solve_check};
+static std::atomic<int> g_schur_sparse_legacy{ba_env().schur_sparse_legacy};
 
 // || (H + diag(ep + lm H_ii)) x - b ||_inf <= 1e-5 (||b||_inf + max_i sum_j |H_ij x_j|)  (x is the float solution: its rounding alone is
 // ~6e-8 of the row sums) -- else dx := 0, meta[1] := 1.  H: lower triangle.  One workgroup, a row per thread at a time.
@@ -172,11 +176,15 @@ int ba_plan(int N, int B, int ht, int wd, int t0, int t1, void *ws, size_t ws_by
   // contributions to the separator block through it (ba_solve_band.hip)
   const bool want_scratch = !lds_fits || (ba_solve_band_supported(n6) && n6 >= 96);
   if (want_scratch) o_lscratch = take(sizeof(double) * ba_solve_scratch_doubles(n6));
+  // (the pair list of the row-pair Schur form: behind everything dba_ba_layout describes, so that no published offset moves)
+  const size_t pairs_cap = (size_t)(P + N) * SCHUR_KP;
+  const size_t o_pairs = take(sizeof(int) * 4 * (1 + pairs_cap));
   L.P = P;
   L.Mmax = Mmax;
   L.nchunks = nchunks;
   plan->layout = L;
   plan->bytes = off;
+  plan->pairs_off = o_pairs, plan->pairs_cap = (int)pairs_cap;
   plan->P = P;
   plan->N = N;
   plan->B = B;
@@ -198,6 +206,8 @@ int ba_plan(int N, int B, int ht, int wd, int t0, int t1, void *ws, size_t ws_by
     plan->T.fhead = reinterpret_cast<int *>(base + o_fhead);
     plan->T.frow = reinterpret_cast<int *>(base + o_frow);
     plan->T.gkey = reinterpret_cast<int *>(base + o_gkey);
+    plan->T.pairs = reinterpret_cast<int *>(base + o_pairs);
+    plan->T.pairs_cap = (int)pairs_cap;
     plan->T.Mmax = Mmax;
     plan->T.B = B;
     plan->W.E = reinterpret_cast<float *>(base + L.E);
@@ -227,7 +237,8 @@ static int ba_prepare_stage(const BaPlan &plan, const int64_t *ii, const int64_t
   const int threads = std::min(1024, std::max(64, (want + 63) / 64 * 64));
   const size_t scan_ints = std::max<size_t>(std::max(threads, P), N > threads ? 1024 : 0) + 32;
   // (+ per-slot row counts for the frame row table: Mmax + 1 ints)
-  const size_t lds = sizeof(int) * ((size_t)B + 2 * (size_t)plan.T.Mmax + 1 + scan_ints + plan.T.Mmax + 1);
+  // (... and per-slot offsets into the pair list of the row-pair form: Mmax + 1 more)
+  const size_t lds = sizeof(int) * ((size_t)B + 2 * (size_t)plan.T.Mmax + 1 + scan_ints + 2 * ((size_t)plan.T.Mmax + 1));
   if (lds > 160 * 1024 || P > 16384) return DBA_ERR_UNSUPPORTED;
   if (lds > 64 * 1024) {
     DBA_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&ba_prepare_kernel),
@@ -294,8 +305,15 @@ static int ba_reduce_stage(const BaPlan &plan, const int64_t *ii, const int64_t 
     // per-source-frame form (every row of E read once, Gram tiles on the matrix cores); DBA_SCHUR_KERNEL=rows keeps
     // the (row, partner) grid, which also takes graphs with more edges than the prepare kernel lists per frame
     if (!ba_schur_frame_form(N, plan.P)) {
-      hipLaunchKernelGGL(ba_schur_kernel, dim3(plan.P + N + ablocks, SCHUR_KP, SCHUR_CH), dim3(256), 0, stream, ii, jj,
-                         frame_owned, N, plan.HW, plan.t0, plan.P, lower, plan.T, plan.W);
+      // one workgroup per listed pair and pixel chunk (the list's length is only known on the device: the grid is sized for the
+      // (row, partner slot) grid's count, the workgroups behind the list leave at once); DBA_SCHUR_SPARSE=legacy or
+      // dba_ba_schur_sparse_select(1) keep the (row, partner slot) grid
+      if (g_schur_sparse_legacy.load(std::memory_order_relaxed))
+        hipLaunchKernelGGL(ba_schur_kernel, dim3(plan.P + N + ablocks, SCHUR_KP, SCHUR_CH), dim3(256), 0, stream, ii, jj,
+                           frame_owned, N, plan.HW, plan.t0, plan.P, lower, plan.T, plan.W);
+      else
+        hipLaunchKernelGGL(ba_schur_pairs_kernel, dim3(ablocks + plan.pairs_cap * SCHUR_CH), dim3(256), 0, stream, ii, jj,
+                           frame_owned, N, plan.HW, plan.t0, plan.P, lower, plan.T, plan.W);
     } else {
       // pixel chunks per frame: ~1024 pixels per workgroup (256 per wave).  A function of the map size alone: a rank of
       // the sharded driver must cut a frame exactly as a single GPU does (same partial sums, bit for bit)
@@ -532,6 +550,21 @@ int dba_ba_get_layout(int N, int B, int ht, int wd, int t0, int t1, dba_ba_layou
   const int rc = ba_plan(N, B, ht, wd, t0, t1, nullptr, 0, &plan);
   if (rc != DBA_OK) return rc;
   *out = plan.layout;
+  return DBA_OK;
+}
+
+int dba_ba_pairs_table(int N, int B, int ht, int wd, int t0, int t1, size_t *offset, int *capacity) {
+  BaPlan plan;
+  const int rc = ba_plan(N, B, ht, wd, t0, t1, nullptr, 0, &plan);
+  if (rc != DBA_OK) return rc;
+  if (offset) *offset = plan.pairs_off;
+  if (capacity) *capacity = plan.pairs_cap;
+  return DBA_OK;
+}
+
+int dba_ba_schur_sparse_select(int legacy) {
+  if (legacy != 0 && legacy != 1) return DBA_ERR_ARG;
+  g_schur_sparse_legacy.store(legacy, std::memory_order_relaxed);
   return DBA_OK;
 }
 

@@ -35,6 +35,13 @@ struct BaTables {
   int *frow;        // [P+N][2]   row of E, pose index (- t0) it belongs to
   int *gkey;        // [8 + 2N]   the graph these tables were built for: magic, N, B, t0, t1, Schur form, Mmax, -, then ii, jj
                     //            as int32 (stage 0 compares a call's edge list with it and skips itself: dba_ba_prepare_keyed)
+  // flat list of the (row, partner) pairs of the Schur complement, for ba_schur_pairs_kernel: one workgroup per entry and pixel
+  // chunk instead of one per (row, partner slot), most of which find no partner on a sparse window
+  int *pairs;       // [1 + pairs_cap][4]  entry 0: {number of pairs, or -1: not listed (more than pairs_cap, or a graph stage 0
+                    //            takes in several passes), 0, 0, 0}; entry 1 + i: row r1, row r2 >= r1 of the same source frame
+                    //            (r2 == r1: the self pair, which also yields the rhs term), tgt1 | tgt2 << 16 (pose - t0 each, both
+                    //            inside the window), slot of the source frame.  Written for the (row, partner) form only
+  int pairs_cap;    // (P + N) * SCHUR_KP: the (row, partner slot) grid's size
   int Mmax, B;
 };
 
@@ -58,6 +65,8 @@ struct BaPlan {  // host-side view of the workspace
   BaBuffers W;
   dba_ba_layout layout;
   size_t bytes;
+  size_t pairs_off;     // byte offset of T.pairs in the workspace (not part of dba_ba_layout: dba_ba_pairs_table)
+  int pairs_cap;
   int P, N, B, HW, nchunks;
   int ht, wd, t0, t1;   // the sizes it was planned for (P = t1 - t0, HW = ht * wd)
 };
@@ -107,6 +116,9 @@ __global__ void ba_assemble_kernel(const int64_t *ii, const int64_t *jj, const u
                                    int t0, int P, int lower, BaTables T, BaBuffers W);
 __global__ void ba_schur_kernel(const int64_t *ii, const int64_t *jj, const uint8_t *frame_owned, int N, int HW,
                                 int t0, int P, int lower, BaTables T, BaBuffers W);
+// the same sums on the flat pair list (T.pairs): grid (ablocks + pairs_cap * SCHUR_CH), assembly workgroups first
+__global__ void ba_schur_pairs_kernel(const int64_t *ii, const int64_t *jj, const uint8_t *frame_owned, int N, int HW,
+                                      int t0, int P, int lower, BaTables T, BaBuffers W);
 __global__ void ba_symmetrize_kernel(double *H, int n);
 struct ExportArg {
   double A[36];   // row-major 6 x 6 (BA2GTSAM's block, depth_video.py:21-23)

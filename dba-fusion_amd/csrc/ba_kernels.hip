@@ -44,7 +44,7 @@ __device__ __forceinline__ int wave_incl_scan(int v, int lane) {
 }
 
 // One workgroup (a multiple of 64 threads, sized by the host to the graph: barriers among 2 waves are several times
-// cheaper than among 16).  LDS (sm): flag[B] cnt[Mmax + 1] kxs[Mmax] scan[max(blockDim, 1024 if N > blockDim)] vcnt[Mmax + 1].
+// cheaper than among 16).  LDS (sm): flag[B] cnt[Mmax + 1] kxs[Mmax] scan[max(blockDim, 1024 if N > blockDim)] vcnt[Mmax + 1] poff[Mmax + 1].
 // The body of stage 0, shared by its own kernel and by the workgroup that the first linearisation of a keyed call carries
 // (ba_linearize_kernel<.., TF = true>): every thread of the workgroup calls it.
 __device__ void ba_prepare_body(int *sm, const int64_t *__restrict__ ii, const int64_t *__restrict__ jj, int N, int B, int t0,
@@ -55,6 +55,7 @@ __device__ void ba_prepare_body(int *sm, const int64_t *__restrict__ ii, const i
   int *kxs = cnt + T.Mmax + 1;
   int *scan = kxs + T.Mmax;
   int *vcnt = scan + scan_ints;      // [Mmax + 1] rows of E per slot (frame row table), then their exclusive scan
+  int *poff = vcnt + T.Mmax + 1;     // [Mmax + 1] first entry of each slot in the pair list (row-pair form)
   const int tid = threadIdx.x, nt = blockDim.x, lane = tid & 63, wave = tid >> 6, nw = nt >> 6;
   const int P = t1 - t0;
   // this thread's first edge stays in registers (the usual graph has at most one edge per thread): the passes
@@ -179,6 +180,9 @@ __device__ void ba_prepare_body(int *sm, const int64_t *__restrict__ ii, const i
   // O(N^2) comparison never goes back to global memory)
   int *sii = scan;
   const int Mv0 = min(M, T.Mmax);
+  // (no pair list for the per-source-frame form, which has its own table, nor from the several-pass fill below: the Schur
+  // launch then walks rowinfo / einfo as ba_schur_kernel does)
+  if (tid == 0 && (ftable || N > nt)) *reinterpret_cast<int4 *>(T.pairs) = make_int4(-1, 0, 0, 0);
   if (N <= nt) {  // the usual case: one pass, the rank stays in a register
     // ... and the frame row table of the per-source-frame Schur kernel is built on the way: slot m couples its own
     // pose row (if the frame is a window pose) and the rows of its out-edges whose target is one, in list order
@@ -186,11 +190,10 @@ __device__ void ba_prepare_body(int *sm, const int64_t *__restrict__ ii, const i
     const bool myvalid = (tid < N) && (slot_of(my_i) >= 0) && (my_j - t0 >= 0) && (my_j - t0 < P);
     constexpr int VBIT = 1 << 30;
     if (tid < N) sii[tid] = (my_i & (VBIT - 1)) | (myvalid ? VBIT : 0);
-    if (ftable)
-      for (int m = tid; m <= T.Mmax; m += nt) {
-        const int pp = (m < Mv0) ? kxs[m] - t0 : -1;
-        vcnt[m] = (pp >= 0 && pp < P) ? 1 : 0;
-      }
+    for (int m = tid; m <= T.Mmax; m += nt) {   // (the pair list of the row-pair form counts the same rows)
+      const int pp = (m < Mv0) ? kxs[m] - t0 : -1;
+      vcnt[m] = (pp >= 0 && pp < P) ? 1 : 0;
+    }
     __syncthreads();
     int vrank = 0;
     if (tid < N) {
@@ -206,12 +209,51 @@ __device__ void ba_prepare_body(int *sm, const int64_t *__restrict__ ii, const i
         }
         pos = cnt[m] + rank;
         T.elist[pos] = tid;
-        if (myvalid && ftable) atomicAdd(&vcnt[m], 1);
+        if (myvalid) atomicAdd(&vcnt[m], 1);
       }
       emit_edge(tid, m, pos, my_j);
     }
     if (!ftable) {
       for (int m = tid; m < T.Mmax; m += nt) T.fhead[4 * m] = -1, T.fhead[4 * m + 2] = 0;
+      // The pair list.  A slot with v rows (its own pose row, if the frame is a window pose, then its out-edges with a pose
+      // inside the window in list order, i.e. ascending edge id) has v (v + 1) / 2 pairs, stored row by row: the row of rank
+      // vr owns the v - vr entries from vr v - vr (vr - 1) / 2 on, its self pair first.  These are exactly the (row, partner)
+      // combinations ba_schur_kernel visits through rowinfo / einfo.
+      __syncthreads();
+      if (wave == 0) {
+        int carry = 0;
+        for (int base = 0; base <= T.Mmax; base += 64) {
+          const int m = base + lane;
+          const int v = (m < T.Mmax) ? vcnt[m] : 0;
+          const int pc = v * (v + 1) / 2;
+          const int w = wave_incl_scan(pc, lane);
+          if (m <= T.Mmax) poff[m] = carry + w - pc;
+          carry += __shfl(w, 63, 64);
+        }
+      }
+      __syncthreads();
+      const int npairs = poff[T.Mmax];
+      const bool listed = npairs <= T.pairs_cap;
+      int4 *pl = reinterpret_cast<int4 *>(T.pairs) + 1;
+      if (tid == 0) *reinterpret_cast<int4 *>(T.pairs) = make_int4(listed ? npairs : -1, 0, 0, 0);
+      if (listed && myvalid) {
+        const int m = slot_of(my_i), v = vcnt[m], pp = kxs[m] - t0, tg = my_j - t0;
+        const int vr = ((pp >= 0 && pp < P) ? 1 : 0) + vrank;
+        int o = poff[m] + vr * v - vr * (vr - 1) / 2;
+        pl[o++] = make_int4(P + tid, P + tid, tg | (tg << 16), m);
+        const int f = my_i & (VBIT - 1);
+        for (int q = tid + 1; q < N; q++)
+          if (sii[q] == (f | VBIT)) pl[o++] = make_int4(P + tid, P + q, tg | (((int)jj[q] - t0) << 16), m);
+      }
+      if (listed)
+        for (int p = tid; p < P; p += nt) {
+          const int m = slot_of(t0 + p);
+          if (m < 0) continue;
+          int o = poff[m];
+          pl[o++] = make_int4(p, p, p | (p << 16), m);
+          for (int q = 0; q < N; q++)
+            if (sii[q] == ((t0 + p) | VBIT)) pl[o++] = make_int4(p, P + q, p | (((int)jj[q] - t0) << 16), m);
+        }
     } else {
     __syncthreads();
     if (wave == 0) {  // exclusive scan of the row counts; vcnt keeps the offsets
@@ -656,7 +698,7 @@ __global__ __launch_bounds__(256, (PPL == 1 ? (MF ? 4 : 2) : 1)) void ba_lineari
   const int m = blockIdx.y;
   if constexpr (TF) {
     if (m == T.Mmax + 1) {  // the appended row: its first workgroup is stage 0 (the staging tiles are its LDS)
-      static_assert(!TF || 4 * FOLD_MAX_B + 2 + FOLD_SCAN_INTS <= 4 * RED_FLOATS, "stage 0 does not fit the staging tiles");
+      static_assert(!TF || 5 * FOLD_MAX_B + 3 + FOLD_SCAN_INTS <= 4 * RED_FLOATS, "stage 0 does not fit the staging tiles");
       if (blockIdx.x == 0)
         ba_prepare_body(reinterpret_cast<int *>(&s_red[0][0]), S0.ii, jj, N, T.B, t0, S0.t1, FOLD_SCAN_INTS, S0.ftable, 1, eta_rows,
                         S0.status, T, S0.band_verdict, S0.max_nt);
@@ -1202,35 +1244,26 @@ __global__ __launch_bounds__(256) void ba_assemble_kernel(const int64_t *__restr
 // source frame at or after r1 (partner 0 is r1 itself, which also yields the rhs term E Q w).
 // Workgroups with blockIdx.x >= P + N (y = z = 0) do the pose-block assembly instead: both parts only add
 // into H, b, so they share one launch (two launches less per call on a ~300 us step).
-__global__ __launch_bounds__(256) void ba_schur_kernel(const int64_t *__restrict__ ii,
-                                                       const int64_t *__restrict__ jj,
-                                                       const uint8_t *__restrict__ frame_owned, int N, int HW,
-                                                       int t0, int P, int lower, BaTables T, BaBuffers W) {
-  __shared__ float red[4][44];
+// schur_rows_body: workgroup (row r1, partner slot ks of nks, pixel chunk ch of nch); also what ba_schur_pairs_kernel runs
+// for a graph whose pairs stage 0 did not list
+__device__ __forceinline__ void schur_rows_body(float (*red)[44], int r1, int ks, int nks, int ch, int nch,
+                                                const uint8_t *__restrict__ frame_owned, int HW, int t0, int P, int lower,
+                                                const BaTables &T, const BaBuffers &W) {
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int n6 = 6 * P;
-  // (round 6: the assembly workgroups come FIRST in the grid -- their chain of partial loads, shuffles and atomics is the longest
-  // in the launch, and dispatched last it was its tail)
-  const int ablk = (N + 3) / 4;
-  if ((int)blockIdx.x < ablk) {
-    if (blockIdx.y == 0 && blockIdx.z == 0)
-      ba_assemble_block((int)blockIdx.x, ii, jj, frame_owned, N, t0, P, lower, T, W);
-    return;
-  }
   // everything a row needs comes from its table row (one load): slot, target pose, partner range, source frame
-  const int r1 = (int)blockIdx.x - ablk;
   const int4 ri = *reinterpret_cast<const int4 *>(T.rowinfo + 8 * r1);
   const int m = ri.x, tgt1 = ri.y, first_partner = ri.z, e1 = ri.w;  // partners: r1 itself, then list positions [first_partner, e1)
   if (m < 0) return;
   if (frame_owned && !frame_owned[T.rowinfo[8 * r1 + 4]]) return;
-  const int chunk = (HW + gridDim.z - 1) / gridDim.z;
-  const int k0 = blockIdx.z * chunk, k1 = min(HW, k0 + chunk);
+  const int chunk = (HW + nch - 1) / nch;
+  const int k0 = ch * chunk, k1 = min(HW, k0 + chunk);
 
   const float *E1 = W.E + (size_t)r1 * 6 * HW;
   const float *Qm = W.Q + (size_t)m * HW;
   const float *wm = W.w + (size_t)m * HW;
 
-  for (int pe = first_partner - 1 + (int)blockIdx.y; pe < e1; pe += gridDim.y) {
+  for (int pe = first_partner - 1 + ks; pe < e1; pe += nks) {
     const bool self = (pe == first_partner - 1);
     const int2 ei = self ? make_int2(0, 0) : *reinterpret_cast<const int2 *>(T.einfo + 2 * pe);
     const int r2 = self ? r1 : P + ei.x;
@@ -1286,6 +1319,178 @@ __global__ __launch_bounds__(256) void ba_schur_kernel(const int64_t *__restrict
       acc_add(&W.b[6 * tgt1 + (tid - 36)], -s, (lower & 2) != 0);
     }
   }
+}
+
+__global__ __launch_bounds__(256) void ba_schur_kernel(const int64_t *__restrict__ ii,
+                                                       const int64_t *__restrict__ jj,
+                                                       const uint8_t *__restrict__ frame_owned, int N, int HW,
+                                                       int t0, int P, int lower, BaTables T, BaBuffers W) {
+  __shared__ float red[4][44];
+  // (round 6: the assembly workgroups come FIRST in the grid -- their chain of partial loads, shuffles and atomics is the longest
+  // in the launch, and dispatched last it was its tail)
+  const int ablk = (N + 3) / 4;
+  if ((int)blockIdx.x < ablk) {
+    if (blockIdx.y == 0 && blockIdx.z == 0)
+      ba_assemble_block((int)blockIdx.x, ii, jj, frame_owned, N, t0, P, lower, T, W);
+    return;
+  }
+  schur_rows_body(red, (int)blockIdx.x - ablk, (int)blockIdx.y, (int)gridDim.y, (int)blockIdx.z, (int)gridDim.z, frame_owned, HW,
+                  t0, P, lower, T, W);
+}
+
+// The same sums, one workgroup per LISTED pair and pixel chunk (T.pairs, written by stage 0): on a sparse window most
+// (row, partner slot) workgroups of the grid above find no partner (25 KF / 96 edges: 338 pairs on 960 slots), and one that
+// has a pair reaches it through rowinfo -> einfo and then pays one round trip to memory per 256 pixels.  Here
+//   * the grid is (pose-block assembly | pair 0 chunk 0, pair 0 chunk 1, pair 1 chunk 0 ... | empty): the workgroups with work are
+//     dispatched first, one behind the list's length leaves on one uniform load, a pair is one 16-byte load;
+//   * a chunk of up to 2048 pixels (the 8 trips of a 64 x 64 map) is loaded in one phase -- 8 x 13 loads in flight, 8 x 8 on a self
+//     pair, which reads its row once -- and only then multiplied, pixel k0 + tid first, then + 256 ...: every accumulator sees the
+//     fmaf sequence of the loop; lanes past the chunk's end load a clamped address and skip the products;
+//   * a self pair whose upper triangle nobody stores forms the 21 products of the lower one;
+//   * the wave's 36 / 42 / 27 sums are formed by one transposing tree (common.h) that joins lanes exactly as the 42
+//     wave_sum_to_lane63 calls do, and meet the other waves' in LDS as before.
+// Which thread sums which pixel, every float sum and the float64 sums of the four waves are those of ba_schur_kernel: in
+// deterministic mode H and b come out bit for bit the same (tests/test_gpu_schur_sparse.py).
+constexpr int SCHUR_BATCH = 8;   // pixels per lane of the one-phase form
+
+template <bool SELF, bool TRI>
+__device__ __forceinline__ void schur_pair_mac(float (&acc)[36], float (&sv)[6], const float (&e1v)[6], const float (&e2v)[6],
+                                               float wk) {
+#pragma unroll
+  for (int a = 0; a < 6; a++)
+#pragma unroll
+    for (int b = 0; b < 6; b++)
+      if (!TRI || a >= b) acc[a * 6 + b] = fmaf(e1v[a], e2v[b], acc[a * 6 + b]);
+  if constexpr (SELF) {
+#pragma unroll
+    for (int c = 0; c < 6; c++) sv[c] = fmaf(e1v[c], wk, sv[c]);
+  }
+}
+
+template <bool SELF, bool TRI>
+__device__ __forceinline__ void schur_pair_block(float (*red)[44], bool batch, const float *__restrict__ E1,
+                                                 const float *__restrict__ E2, const float *__restrict__ Qm,
+                                                 const float *__restrict__ wm, int HW, int k0, int k1, int tgt1, int tgt2,
+                                                 int n6, int lower, const BaBuffers &W) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  float acc[36];
+  float sv[6];
+#pragma unroll
+  for (int c = 0; c < 36; c++) acc[c] = 0.f;
+#pragma unroll
+  for (int c = 0; c < 6; c++) sv[c] = 0.f;
+  if (batch) {
+    constexpr int U = SCHUR_BATCH;
+    float q[U], ea[U][6], eb[SELF ? 1 : U][6], wk[SELF ? U : 1];
+    const int kb = k0 + tid;
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      const int kk = min(kb + 256 * u, HW - 1);   // (past the chunk: any valid address, the value is not used)
+      q[u] = Qm[kk];
+#pragma unroll
+      for (int c = 0; c < 6; c++) {
+        ea[u][c] = E1[(size_t)c * HW + kk];
+        if constexpr (!SELF) eb[u][c] = E2[(size_t)c * HW + kk];
+      }
+      if constexpr (SELF) wk[u] = wm[kk];
+    }
+    __builtin_amdgcn_sched_barrier(0);   // every load above is issued before the first product below
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      if (kb + 256 * u < k1) {
+        float e1v[6], e2v[6];
+#pragma unroll
+        for (int c = 0; c < 6; c++) {
+          e1v[c] = ea[u][c] * q[u];
+          e2v[c] = SELF ? ea[u][c] : eb[SELF ? 0 : u][c];
+        }
+        schur_pair_mac<SELF, TRI>(acc, sv, e1v, e2v, SELF ? wk[SELF ? u : 0] : 0.f);
+      }
+    }
+  } else {
+    for (int k = k0 + tid; k < k1; k += 256) {
+      const float q = Qm[k];
+      float e1v[6], e2v[6];
+#pragma unroll
+      for (int c = 0; c < 6; c++) {
+        const float e = E1[(size_t)c * HW + k];
+        e1v[c] = e * q;
+        e2v[c] = SELF ? e : E2[(size_t)c * HW + k];
+      }
+      schur_pair_mac<SELF, TRI>(acc, sv, e1v, e2v, SELF ? wm[k] : 0.f);
+    }
+  }
+  // the wave's sums: value c < NP is product c (TRI: entry a (a + 1) / 2 + b of the lower triangle), then the 6 rhs terms
+  constexpr int NP = TRI ? 21 : 36, NV = NP + (SELF ? 6 : 0);
+  float v[NV];
+#pragma unroll
+  for (int a = 0; a < 6; a++)
+#pragma unroll
+    for (int b = 0; b < 6; b++) {
+      if constexpr (!TRI) v[a * 6 + b] = acc[a * 6 + b];
+      else if (a >= b) v[a * (a + 1) / 2 + b] = acc[a * 6 + b];
+    }
+  if constexpr (SELF) {
+#pragma unroll
+    for (int c = 0; c < 6; c++) v[NP + c] = sv[c];
+  }
+  int idx;
+  const float r = wave_sum_transpose<NV>(v, lane, idx);
+  if (idx >= 0) red[wv][idx] = r;
+  __syncthreads();
+  if (tid < NV) {
+    const double s = (double)red[0][tid] + (double)red[1][tid] + (double)red[2][tid] + (double)red[3][tid];
+    const bool fixed = (lower & 2) != 0;
+    if (tid < NP) {
+      int a, b;
+      if constexpr (TRI) {
+        a = 0;
+        while ((a + 1) * (a + 2) / 2 <= tid) a++;
+        b = tid - a * (a + 1) / 2;
+      } else {
+        a = tid / 6, b = tid % 6;
+      }
+      if constexpr (!SELF) h_add_pair(W, n6, 6 * tgt1 + a, 6 * tgt2 + b, -s, (lower & 1) != 0, fixed);
+      else acc_add(&W.H[(size_t)(6 * tgt1 + a) * n6 + 6 * tgt2 + b], -s, fixed);
+    } else {
+      acc_add(&W.b[6 * tgt1 + (tid - NP)], -s, fixed);
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void ba_schur_pairs_kernel(const int64_t *__restrict__ ii,
+                                                             const int64_t *__restrict__ jj,
+                                                             const uint8_t *__restrict__ frame_owned, int N, int HW,
+                                                             int t0, int P, int lower, BaTables T, BaBuffers W) {
+  __shared__ float red[4][44];
+  const int ablk = (N + 3) / 4;
+  if ((int)blockIdx.x < ablk) {
+    ba_assemble_block((int)blockIdx.x, ii, jj, frame_owned, N, t0, P, lower, T, W);
+    return;
+  }
+  const int wg = (int)blockIdx.x - ablk;   // < (P + N) * SCHUR_KP * SCHUR_CH
+  const int np = T.pairs[0];
+  if (np < 0) {   // no list for this graph: the (row, partner slot, chunk) walk
+    schur_rows_body(red, wg / (SCHUR_KP * SCHUR_CH), (wg / SCHUR_CH) % SCHUR_KP, SCHUR_KP, wg % SCHUR_CH, SCHUR_CH, frame_owned,
+                    HW, t0, P, lower, T, W);
+    return;
+  }
+  const int pi = wg / SCHUR_CH, ch = wg % SCHUR_CH;
+  if (pi >= np) return;
+  const int4 pr = reinterpret_cast<const int4 *>(T.pairs)[1 + pi];
+  const int r1 = pr.x, r2 = pr.y, tgt1 = pr.z & 0xffff, tgt2 = pr.z >> 16, m = pr.w;
+  if (frame_owned && !frame_owned[T.kx[m]]) return;
+  const int chunk = (HW + SCHUR_CH - 1) / SCHUR_CH;
+  const int k0 = ch * chunk, k1 = min(HW, k0 + chunk);
+  const bool batch = chunk <= 256 * SCHUR_BATCH;
+  const float *E1 = W.E + (size_t)r1 * 6 * HW;
+  const float *E2 = W.E + (size_t)r2 * 6 * HW;
+  const float *Qm = W.Q + (size_t)m * HW;
+  const float *wm = W.w + (size_t)m * HW;
+  const int n6 = 6 * P;
+  if (r1 != r2) schur_pair_block<false, false>(red, batch, E1, E2, Qm, wm, HW, k0, k1, tgt1, tgt2, n6, lower, W);
+  else if (lower & 1) schur_pair_block<true, true>(red, batch, E1, E2, Qm, wm, HW, k0, k1, tgt1, tgt2, n6, lower, W);
+  else schur_pair_block<true, false>(red, batch, E1, E2, Qm, wm, HW, k0, k1, tgt1, tgt2, n6, lower, W);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -69,6 +69,58 @@ __device__ __forceinline__ float wave_sum_to_lane63(float x) {
   return x;
 }
 
+// Sums of N values per lane over the wave at once, by a transposing tree.
+//
+// wave_sum_to_lane63 pairs lanes as a balanced binary tree over ADJACENT, ALIGNED lane blocks: row_shr:1 forms x[2i+1] + x[2i]
+// (in the odd lanes that lane 63's result is made of), row_shr:2 adds the sums of two neighbouring pairs, row_shr:4 and :8 those
+// of neighbouring 4- and 8-lane blocks, row_bcast:15 adds row 0 to row 1 and row 2 to row 3, row_bcast:31 adds (rows 0 + 1) to
+// (rows 2 + 3).  Lane 63 never takes in one of the zeros that lanes without a source receive.  A float add is commutative, so
+// the total is a function of that tree alone:  level b joins the sums of the two 2^b-lane blocks that differ in lane bit b.
+//
+// The tree below does the same joins for every value, but each of them in ONE lane of a pair instead of in both: at level b a
+// lane keeps the first half of its values if its bit b is clear and the second half if it is set, hands the other half to lane
+// ^ 2^b and adds what it receives -- block sum + block sum, the same two floats wave_sum_to_lane63 adds.  N values take
+// N/2 + N/4 + ... ~ N adds instead of 6 N.  After the six levels a lane holds the wave's total of ONE value: the return value,
+// of value `idx` (-1: the lane holds none; every value 0 .. N - 1 ends in exactly one lane).
+template <int MASK>
+__device__ __forceinline__ float lane_xor_get(float x) {
+  if constexpr (MASK == 1) return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0xB1, 0xf, 0xf, false));   // quad_perm [1,0,3,2]
+  else if constexpr (MASK == 2) return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x4E, 0xf, 0xf, false));  // quad_perm [2,3,0,1]
+  else if constexpr (MASK == 8) return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x128, 0xf, 0xf, false));  // row_ror:8
+  else return __shfl_xor(x, MASK, 64);
+}
+template <int N, int BIT>
+__device__ __forceinline__ float wave_sum_transpose_level(const float (&v)[N], int lane, int &pos, bool &ok) {
+  constexpr int H = (N + 1) / 2;
+  const bool up = (lane & BIT) != 0;
+  float k[H];
+#pragma unroll
+  for (int i = 0; i < H; i++) {
+    const float hi = (H + i < N) ? v[H + i] : 0.f;   // (an odd level: the upper half is one short, its last sum is nobody's)
+    const float keep = up ? hi : v[i], send = up ? v[i] : hi;
+    k[i] = keep + lane_xor_get<BIT>(send);
+  }
+  float r;
+  if constexpr (BIT == 32) {
+    static_assert(H == 1, "at most 64 values");
+    r = k[0], pos = 0, ok = true;
+  } else {
+    r = wave_sum_transpose_level<H, 2 * BIT>(k, lane, pos, ok);
+  }
+  pos = up ? H + pos : pos;   // the position, among this level's N values, of the one the lane ends up with
+  ok = ok && pos < N;
+  return r;
+}
+template <int N>
+__device__ __forceinline__ float wave_sum_transpose(const float (&v)[N], int lane, int &idx) {
+  static_assert(N >= 1 && N <= 64, "one value per lane at the end");
+  int pos;
+  bool ok;
+  const float r = wave_sum_transpose_level<N, 1>(v, lane, pos, ok);
+  idx = ok ? pos : -1;
+  return r;
+}
+
 // total broadcast to every lane (via SGPR)
 __device__ __forceinline__ float wave_sum(float x) {
   x = wave_sum_to_lane63(x);

@@ -88,6 +88,8 @@ SYMBOLS = {
     "dba_ba_schur_auto_form": (c_int, [c_int, c_int]),
     "dba_ba_schur_thread_form": (c_int, []),
     "dba_ba_schur_generation": (c_int, []),
+    "dba_ba_schur_sparse_select": (c_int, [c_int]),
+    "dba_ba_pairs_table": (c_int, [c_int] * 6 + [ctypes.POINTER(c_size_t), ctypes.POINTER(c_int)]),
     "dba_ba_set_deterministic": (c_int, [c_int]),
     "dba_ba_set_solve_check": (c_int, [c_int]),
     "dba_ba_solve_check": (c_int, [c_int] * 6 + [c_float, c_float, _P, c_size_t, _P]),

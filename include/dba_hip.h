@@ -146,6 +146,14 @@ int dba_ba_schur_auto_form(int N, int P); /* the form (1 or 2) the automatic cho
                                            * the call (a rank's share has the same rows per frame, but few edges) */
 int dba_ba_schur_generation(void); /* number of dba_ba_schur_select calls so far: tables prepared under another generation
                                     * may lack what the form in force needs (callers of dba_ba_prepared compare it) */
+/* How the (row, partner) form walks its pairs: 0 = one workgroup per pair of the list stage 0 leaves in the workspace, with a
+ * chunk's pixels loaded in one phase and one transposing reduction per wave; 1 = the (row, partner slot) grid.  Both form the
+ * same sums (bit for bit in deterministic mode) and read the same tables, so the switch may change between any two calls.
+ * Initialised from DBA_SCHUR_SPARSE = legacy. */
+int dba_ba_schur_sparse_select(int legacy);
+/* where that list lies in the workspace (bytes from its start) and how many pairs it holds at most: int32 [1 + capacity][4],
+ * entry 0 = {number of pairs or -1 (not listed), 0, 0, 0}, entry 1 + i = {row r1, row r2, tgt1 | tgt2 << 16, slot} */
+int dba_ba_pairs_table(int N, int B, int ht, int wd, int t0, int t1, size_t *offset, int *capacity);
 
 /* Deterministic accumulation of H, b (off by default; DBA_DETERMINISTIC=1 turns it on at load).  The reference adds the
  * blocks of the camera system on the host in a fixed order (SparseBlock::update_lhs / update_rhs, droid_kernels.cu:1176-1218);
