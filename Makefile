@@ -23,7 +23,7 @@ oracle:
 
 # kernels whose results must be bit-identical to the reference arithmetic: no mul+add fusion
 # (HIP's default -ffp-contract=fast fuses in the backend regardless of source pragmas)
-EXACT := corr_lookup corr_sheared altcorr update_inputs gru extractor update_op conv3x3 conv1x1 conv7x7 conv_enc
+EXACT := corr_lookup corr_sheared altcorr update_inputs gru extractor update_op conv3x3 conv3x3_mean conv1x1 conv7x7 conv_enc
 $(foreach f,$(EXACT),$(eval $(BUILD)/$(f).o: EXTRA := -ffp-contract=off))
 
 $(BUILD)/%.o: $(CSRC)/%.hip $(HDRS)

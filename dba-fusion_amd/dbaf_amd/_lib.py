@@ -206,6 +206,9 @@ SYMBOLS = {
     "dba_conv3x3_gates_f16": (c_int, [_P, c_int, _P, c_int, c_int, c_int] + [_P] * 5 + [c_int] * 4 + [_P, _P, _P]),
     "dba_conv3x3_blend_f16": (c_int, [_P, c_int, _P, c_int, c_int, c_int] + [_P] * 5 + [c_int] * 4 + [_P, _P]),
     "dba_conv3x3_pair_f16": (c_int, [_P, c_int, _P, c_int, c_int, c_int, _P, _P] + [c_int] * 5 + [_P, _P, _P]),
+    "dba_frame_members_max_slots": (c_int, []),
+    "dba_frame_members": (c_int, [_P, c_int, c_int, _P, _P, _P]),
+    "dba_conv3x3_mean_f16": (c_int, [_P, c_int, _P, _P] + [c_int] * 4 + [_P, _P, c_int, _P, c_int, _P]),
     "dba_conv1x1_tile": (c_int, []),
     "dba_conv1x1_f16": (c_int, [_P, c_int, _P, _P] + [c_int] * 4 + [_P, _P]),
     "dba_conv1x1_context_workspace_bytes": (c_size_t, [c_int] * 3),

@@ -14,6 +14,12 @@ the 7x7 flow stem; nothing else does.
   conv3x3_blend(x, packed, gq, z, net, ..., out)   -> (1 - z) net + z tanh(convq(.) + gq): convq and blend in one launch
   conv3x3_pair(x, packed, relu=False)              -> (conv_a(x), conv_b(x)) for pack_weights((conv_a, conv_b)): one launch,
                                      two contiguous tensors (the heads' delta[0] / weight[0])
+  conv3x3_frame_mean(x, packed, inverse, dim_size, out=None, table=None)
+                                     scatter_mean(conv3x3(x, packed, relu=True), inverse, dim=0, dim_size=dim_size) in ONE launch
+                                     (csrc/conv3x3_mean.hip): the bytes of those two calls, the [n, C_out, h, w] tensor between
+                                     them never written.  table: frame_members(inverse, dim_size), made here when not given
+  frame_mean_pays(frames, h, w, compute_units)      the switch's routing rule on frames x tiles (measured; see its docstring)
+  frame_members(inverse, dim_size)   -> (seg_start [dim_size + 1], members [n]) int32: each slot's edges, ascending; one launch
   supported(c0, c1, c_out)           the kernels' channel constraints: c0 % 32 == 0, c1 % 32 == 0, c_out % 64 == 0
 
 and the 1x1 convolutions as a GEMM on the same matrix instruction (csrc/conv1x1.hip); C_in any positive count, C_out % 64 == 0:
@@ -242,6 +248,91 @@ def conv3x3(x, weight, bias=None, relu=False, x1=None, x1_first=0, x1_channels=N
         _lib.check(_lib.load().dba_conv3x3_f16(*_src_args(x, c0, x1, c1, c1_total, first), _p(pk.w), _p(pk.bias), c_out, n, h, w,
                                                int(bool(relu)), _p(out), _lib.stream(x.device)), "dba_conv3x3_f16")
     return out
+
+
+def frame_members_max_slots():
+    """the most slots a member table covers (the frame plan's most rows)"""
+    return int(_lib.load().dba_frame_members_max_slots())
+
+
+def frame_mean_pays(frames, h, w, compute_units):
+    """GraphAgg.fuse_mean's routing rule on frames x tiles, a pure function: does ONE launch of frames x tiles x 2 long
+    workgroups (each runs all its slot's members) beat conv3x3 + scatter_mean?  The device holds 2 workgroups of this kernel
+    per compute unit.  Measured (profiles/conv_agg_mean_bench.json, 256 compute units, five states): the launch met DESIGN
+    4.17's bar where its last round of workgroups filled 0.75 and 0.75, 0.75 of the device (384, 384 and 896 workgroups) and
+    missed it at 0.47 and 0.56 (240 and 800).  So: a last round under three quarters full keeps the two launches.  Grids of
+    at most an eighth of a round (the tests' windows) were not timed; there one launch replaces two that are both bound by
+    their launch, and they take the one launch."""
+    t = 16
+    grid = int(frames) * ((int(h) + t - 1) // t) * ((int(w) + t - 1) // t) * 2
+    room = 2 * int(compute_units)
+    if grid <= room // 8:
+        return True
+    last = grid % room
+    return last == 0 or 4 * last >= 3 * room
+
+
+def frame_members(inverse, dim_size):
+    """the member table of a frame plan: (seg_start [dim_size + 1], members [n]) int32 on inverse's device, with
+    members[seg_start[s]:seg_start[s + 1]] the positions e of inverse == s in ascending order (a stable counting sort in one
+    small launch, dba_frame_members; no host read).  Entries of inverse outside [0, dim_size) belong to no slot, as
+    scatter_mean(dim_size=) ignores them; the tail of members behind seg_start[dim_size] is -1."""
+    op = "frame_members"
+    _lib.dev_tensor(op, inverse, "inverse", None, torch.int64)
+    _lib.require(inverse.dim() == 1 and inverse.shape[0] >= 1, op, "inverse must be a non-empty 1-D list, got %s" % (tuple(inverse.shape),))
+    lib = _lib.load()
+    most = int(lib.dba_frame_members_max_slots())
+    _lib.require(int(dim_size) == dim_size and 1 <= int(dim_size) <= most, op, "dim_size must be an integer in 1 .. %d, got %r" % (most, dim_size))
+    n, F, dev = int(inverse.shape[0]), int(dim_size), inverse.device
+    with torch.cuda.device(dev):
+        seg_start = torch.empty(F + 1, dtype=torch.int32, device=dev)
+        members = torch.empty(n, dtype=torch.int32, device=dev)
+        _lib.check(lib.dba_frame_members(_p(inverse), n, F, _p(seg_start), _p(members), _lib.stream(dev)), "dba_frame_members")
+    return seg_start, members
+
+
+def conv3x3_frame_mean(x, packed, inverse, dim_size, out=None, table=None):
+    """scatter_mean(conv3x3(x, packed, relu=True), inverse, dim=0, dim_size=dim_size) in ONE launch, byte for byte: per slot
+    the members' convolutions in ascending edge order, each rounded to half through the ReLU as conv3x3 stores it, added as
+    floats from 0, divided by max(count, 1) and rounded once.  x [n, C_in, h, w] half, packed: pack_weights(conv), inverse
+    [n] int64 (frame_plan's; entries outside [0, dim_size) belong to no slot), table: frame_members(inverse, dim_size) when the
+    caller keeps it with its plan.  -> [dim_size, C_out, h, w] half, an empty slot zeros.
+
+    The result is allocated here; a caller's `out` must be a contiguous half [rows >= dim_size, C_out, h, w] on x's device
+    that shares no byte with an input, else ValueError before anything is launched (then out[:dim_size] is returned).  The
+    library is told the rows `out` really has (out.shape[0]), never dim_size again: it refuses dim_size > rows itself."""
+    op = "conv3x3_frame_mean"
+    _require(isinstance(packed, Packed), "conv3x3_frame_mean takes pack_weights' result")
+    pk, n, h, w, c_in, _, _, _, c_out = _inputs(x, packed, None, None, 0, None)
+    _lib.dev_tensor(op, inverse, "inverse", x.device, torch.int64)
+    _lib.require(inverse.dim() == 1 and inverse.shape[0] == n, op, "inverse must be [%d], got %s" % (n, tuple(inverse.shape)))
+    _lib.require(int(dim_size) == dim_size and int(dim_size) >= 1, op, "dim_size must be a positive integer, got %r" % (dim_size,))
+    F = int(dim_size)
+    if out is not None:   # refused here, before the library is touched
+        _lib.require(isinstance(out, torch.Tensor) and out.is_cuda and out.device == x.device, op, "out must be a HIP device tensor on %s" % x.device)
+        _lib.require(out.dtype == torch.float16, op, "out must be float16, got %s" % out.dtype)
+        _lib.require(out.dim() == 4 and tuple(out.shape[1:]) == (c_out, h, w), op, "out must be [rows, %d, %d, %d], got %s"
+                     % (c_out, h, w, tuple(out.shape)))
+        _lib.require(out.shape[0] >= F, op, "out holds %d rows, dim_size is %d" % (out.shape[0], F))
+        _lib.require(out.is_contiguous(), op, "out must be contiguous")
+        for t, tnm in ((x, "x"), (pk.w, "the weights"), (pk.bias, "the bias"), (inverse, "inverse")):
+            _lib.require(t is None or not _overlap(out, t), op, "out overlaps %s" % tnm)
+    lib = _lib.load()
+    most = int(lib.dba_frame_members_max_slots())
+    _lib.require(F <= most, op, "dim_size must be at most %d, got %d" % (most, F))
+    if out is None:
+        out = torch.empty((F, c_out, h, w), dtype=torch.float16, device=x.device)
+    if table is None:
+        table = frame_members(inverse, F)
+    seg_start, members = table
+    for t, nm, size in ((seg_start, "seg_start", F + 1), (members, "members", n)):
+        _lib.dev_tensor(op, t, "table: " + nm, x.device, torch.int32)
+        _lib.require(tuple(t.shape) == (size,), op, "table: %s must be [%d], got %s" % (nm, size, tuple(t.shape)))
+        _lib.require(not _overlap(out, t), op, "out overlaps the table")
+    with torch.cuda.device(x.device):
+        _lib.check(lib.dba_conv3x3_mean_f16(_p(x), c_in, _p(pk.w), _p(pk.bias), c_out, n, h, w, _p(seg_start), _p(members), F,
+                                            _p(out), int(out.shape[0]), _lib.stream(x.device)), "dba_conv3x3_mean_f16")
+    return out if out.shape[0] == F else out[:F]
 
 
 def _gate_term(g, nm, x, n, c):

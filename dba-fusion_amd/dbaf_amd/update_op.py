@@ -53,6 +53,14 @@ ONE heads launch with Head.out_dtype = torch.float32 (v = s + b rounded once to 
 the dtype the statements return); the 128 -> 576 mask convolution is conv1x1 wherever forward called self.upmask(net), and
 an UpmaskSource made under the switch materializes through conv1x1 too.  With fuse_conv and fuse_flow_stem as well, a forward
 with upsample=True makes no stock convolution call, under autocast or not.  Each piece routes on its own facts.
+
+fuse_mean (default off: then nothing changes; GraphAgg's switch, UpdateModule.fuse_mean forwards to it; independent of the four
+others): conv1, its ReLU and the mean over each frame's edges are ONE launch (dbaf_amd.conv.conv3x3_frame_mean), with the bytes
+of conv3x3(relu=True) + scatter_mean(dim_size=F); the [N, 128, ht, wd] tensor between them is never written.  It takes effect
+where conv3x3's own facts hold for conv1 (contiguous half device tensors, nothing asking for a gradient) and batch == 1;
+everything else keeps its present route, and so does a window whose frames x tiles grid conv.frame_mean_pays sends back to
+the two launches (measured slower there).  The member table of an edge list is kept with its plan (frame_members): a standing
+list launches nothing for it and reads nothing from the host.
 """
 import ctypes
 
@@ -216,6 +224,7 @@ def clear_cast_cache(module):
 PLAN_MAX_EDGES = 8192    # per list, the limit of dbaf_amd.factors
 plan_stats = dict(launches=0, host_reads=0)   # of frame_plan since import, as dbaf_amd.update_inputs.stats
 _PLAN_MEMO = _lib.EdgeSetMemo()   # edge lists whose n_uniq is known: key (buffer,), value n_uniq
+_MEMBERS_MEMO = _lib.EdgeSetMemo()   # edge lists whose member table is made: key (n_uniq,), value (seg_start, members)
 
 
 def plan_max_rows():
@@ -241,6 +250,7 @@ def frame_plan(ii, buffer):
     c = (ctypes.c_int * 6)()
     if lib.dba_frame_plan_poll(c):
         _PLAN_MEMO.clear()
+        _MEMBERS_MEMO.clear()
         raise RuntimeError("frame_plan (MI355X): an earlier call found n_uniq = %d with %d entries out of range (first at %d) "
                            "on the device, its results were sized for n_uniq = %d: the edge list was written without torch "
                            "noticing" % (c[0], c[1], c[2], c[3]))
@@ -264,6 +274,19 @@ def frame_plan(ii, buffer):
     return uniq[:expect], inverse
 
 
+def frame_members(ii, inverse, dim_size):
+    """conv.frame_members(inverse, dim_size) for the edge list `ii` whose plan gave `inverse`, kept with the list as
+    frame_plan keeps its count: the same tensor object at the same in-place version finds its table again, launches nothing
+    and reads nothing from the host.  Nothing is kept during a stream capture (the table would live in the graph's pool)
+    unless an eager call has made it before; a report of the plan's guard forgets every table."""
+    kept = _MEMBERS_MEMO.lookup((ii,), (int(dim_size),))
+    if kept is None:
+        kept = _conv.frame_members(inverse, dim_size)
+        if not torch.cuda.is_current_stream_capturing():
+            _MEMBERS_MEMO.remember((ii,), (int(dim_size),), kept)
+    return kept
+
+
 def _scatter_mean_plain(src, ix, dim_size):
     """scatter_mean(src [b, n, ...], ix [n], dim=1) in plain torch ops, on any device"""
     out = torch.zeros((src.shape[0], dim_size) + tuple(src.shape[2:]), dtype=src.dtype, device=src.device)
@@ -281,6 +304,8 @@ class GraphAgg(nn.Module):
     fuse_conv = False    # conv1 / conv2 with their ReLUs through dbaf_amd.conv.conv3x3 where its conditions hold
     fuse_agg = False     # conv1 / conv2 as under fuse_conv, eta under autocast in one launch, the mask convolution as conv1x1
                          # (module docstring); independent of the three other switches
+    fuse_mean = False    # conv1, its ReLU and the frame mean in ONE launch (conv.conv3x3_frame_mean) where conv3x3's facts hold
+                         # for conv1 and batch == 1; independent of the four other switches
     plan_rows = None     # None: the most the plan kernel covers
     last_uniq = None
 
@@ -305,6 +330,10 @@ class GraphAgg(nn.Module):
         net = net.view(batch * num, ch, ht, wd)
         uniq, ix = self._plan(ii, plain)
         self.last_uniq = uniq
+        if self._mean_fusable(net, ix, uniq, batch, plain):
+            net = _conv.conv3x3_frame_mean(net, _conv.pack_weights(self.conv1), ix, int(uniq.shape[0]),
+                                           table=frame_members(ii, ix, int(uniq.shape[0])))
+            return self._conv_relu(self.conv2, net, plain), batch, ht, wd
         net = self._conv_relu(self.conv1, net, plain)
         net = net.view(batch, num, 128, ht, wd)
         if plain:
@@ -314,6 +343,15 @@ class GraphAgg(nn.Module):
             net = scatter_mean(net, ix, dim=1, dim_size=int(uniq.shape[0]))   # sized by the plan: no index.max() read
         net = net.view(-1, 128, ht, wd)
         return self._conv_relu(self.conv2, net, plain), batch, ht, wd
+
+    def _mean_fusable(self, net, ix, uniq, batch, plain):
+        """fuse_mean's facts: conv3x3's own for conv1 on net, one batch, a plan with at least one frame on net's device"""
+        return (self.fuse_mean and not plain and batch == 1 and _conv.conv_fusable(self.conv1, net)
+                and not _asks_gradient(self, (net,)) and ix.is_cuda and ix.device == net.device and ix.dtype == torch.int64
+                and ix.dim() == 1 and ix.is_contiguous() and ix.shape[0] == net.shape[0]
+                and 1 <= uniq.shape[0] <= _conv.frame_members_max_slots()
+                and _conv.frame_mean_pays(uniq.shape[0], net.shape[2], net.shape[3],
+                                          torch.cuda.get_device_properties(net.device).multi_processor_count))
 
     def _conv_relu(self, conv, x, plain):
         if (not plain and (self.fuse_conv or self.fuse_agg) and _conv.conv_fusable(conv, x)
@@ -398,6 +436,15 @@ class UpdateModule(nn.Module):
     @fuse_agg.setter
     def fuse_agg(self, on):
         self.agg.fuse_agg = bool(on)
+
+    # GraphAgg's switch under the operator's name: conv1, its ReLU and the frame mean in one launch
+    @property
+    def fuse_mean(self):
+        return self.agg.fuse_mean
+
+    @fuse_mean.setter
+    def fuse_mean(self, on):
+        self.agg.fuse_mean = bool(on)
 
     # flow_encoder[0] with its ReLU as ONE dbaf_amd.conv.conv7x7 launch where stem_fusable holds; a switch of its own,
     # independent of fuse_conv

@@ -1026,6 +1026,32 @@ int dba_conv3x3_blend_f16(const void *src0, int c0, const void *src1, int c1, in
 int dba_conv3x3_pair_f16(const void *src0, int c0, const void *src1, int c1, int c1_total, int src1_first, const void *weight,
                          const void *bias, int c, int n, int h, int w, int relu, void *out0, void *out1, dba_stream_t stream);
 
+/* ---- 3x3 convolution with the frame mean behind it (csrc/conv3x3_mean.hip) -----------------------------------------------
+ * GraphAgg's `scatter_mean(relu(conv1(net)), ix, dim=1)` (dbaf/droid_net.py:57-65) in ONE launch: the [n, C_out, h, w] tensor
+ * between dba_conv3x3_f16(relu = 1) and dba_segment_reduce(mean = 1, dim_size = F) is never written, and out has the bytes
+ * of those two launches.
+ * dba_frame_members: the member table of a plan.  inverse [n] int64 (dba_frame_plan's), F slots, 1 <= F <=
+ *   dba_frame_members_max_slots(); seg_start [F + 1] int32, members [n] int32: members[seg_start[s] .. seg_start[s + 1]) are
+ *   the edges e with inverse[e] == s, ascending (a stable counting sort, one launch of one workgroup, no atomics); entries of
+ *   inverse outside [0, F) belong to no slot, as dba_segment_reduce ignores them; members behind seg_start[F] are -1.
+ * dba_conv3x3_mean_f16: src [n, c_in, h, w] half, weight [9][c_out][c_in] and bias as dba_conv3x3_f16 takes them (one source),
+ *   seg_start [F + 1], members [n] as dba_frame_members writes them, out [out_rows, c_out, h, w] half:
+ *     out[s] = half(sum over the members e of slot s, ascending, of float(relu(half(conv(src[e]) + bias))) / float(max(count, 1)))
+ *   for s < F, a float32 sum from 0 and an IEEE division; rows [F, out_rows) are not touched; an empty slot is zeros.
+ *   out_rows is the number of [c_out, h, w] rows that `out` HOLDS, and F <= out_rows is checked here.  It exists because a
+ *   launch writes F rows and a C caller's F says nothing about the buffer behind `out`: an earlier form of this entry took
+ *   F alone, was called with F beyond its buffer and faulted the device.  A caller passes the row count of the allocation
+ *   itself (dbaf_amd.conv.conv3x3_frame_mean passes out.shape[0]), never F again.
+ *   Returns DBA_ERR_ARG BEFORE ANY HIP RUNTIME CALL when F < 1, F > out_rows, n < 1, an extent <= 0, src, weight, seg_start,
+ *   members or out is null, c_in % 32 or c_out % 64 is not 0, weight is not 16-byte aligned (the tables 4-byte, the halves
+ *   2-byte), h * w * channels of one image or the grid exceeds 2^31 - 1, or out[0 .. F) shares a byte with an input.
+ *   Whatever the tables hold, the kernel reads seg_start[0 .. F], members[0 .. n) and rows [0, n) of src only: a slot's
+ *   bounds are clamped to [0, n] and a member outside [0, n) is skipped. */
+int dba_frame_members_max_slots(void);
+int dba_frame_members(const int64_t *inverse, int n, int F, int *seg_start, int *members, dba_stream_t stream);
+int dba_conv3x3_mean_f16(const void *src, int c_in, const void *weight, const void *bias, int c_out, int n, int h, int w,
+                         const int *seg_start, const int *members, int F, void *out, int out_rows, dba_stream_t stream);
+
 /* ---- 1x1 convolutions on the matrix cores, with the ConvGRU's context chain behind one (csrc/conv1x1.hip) ---------------
  * nn.Conv2d(C_in, C_out, 1) on half tensors [n, C, hw] (the plane flattened): a GEMM on mfma_f32_16x16x32_f16,
  *   c[n, o, p] = half(sum_i W[o, i] * x[n, i, p] + float(b[o])),
