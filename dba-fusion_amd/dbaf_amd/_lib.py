@@ -121,6 +121,9 @@ SYMBOLS = {
                                         ctypes.c_double, ctypes.POINTER(ctypes.c_void_p)]),
     "dba_bacore_retract": (c_int, [_P] * 4 + [c_int] * 6 + [_P, _P, _P, _P, c_size_t, _P]),
     "dba_bacore_optimize": (c_int, [_P, _P] + [c_int] * 6 + [c_float, c_float, _P, _P, c_size_t, _P]),
+    "dba_ba_depth_variance_scratch_bytes": (c_size_t, [c_int]),
+    "dba_ba_depth_variance": (c_int, [c_int] * 6 + [c_float, c_float, _P, c_int, _P, c_size_t, _P, c_size_t, _P]),
+    "dba_ba_depth_variance_parts": (c_int, [c_int] * 6 + [c_float, c_float, _P, c_int, _P, c_size_t, _P, c_size_t, _P, c_int]),
     "dba_corr_index_forward": (c_int, [_P, _P, _P] + [c_int] * 7 + [_P]),
     "dba_corr_lookup_pyramid": (c_int, [_P, _P, _P] + [c_int] * 8 + [_P]),
     "dba_corr_volume_build_sheared_supported": (c_int, [c_int] * 6),

@@ -537,6 +537,47 @@ class BACore:
         self.dx = dx
         return [dx, dz_full[:_num_kx(self.eta, self.ii, self.t0, self.t1, self.ht, self.wd)]]
 
+    def depth_variance(self, out=None, lm=None, ep=None):
+        """Marginal variance of every inverse depth of the window, [B, ht, wd] float32, from the system the last hessian() /
+        hessian_gtsam() left in the workspace (dba_ba_depth_variance, include/dba_hip.h: Q + Q^2 e^T (H + damping)^-1 e per
+        pixel, in float64).  Not a reference binding.  Valid from hessian() until the next one, before or after retract():
+        neither the solvers nor the retraction modify H, E or Q.  A fresh result holds NaN in the rows of frames outside kx;
+        a supplied `out` keeps what it had there.  lm / ep default to init's.  Three launches, no host synchronisation."""
+        assert self._ready, "BACore.init must be called first"
+        if self._linearised is None:
+            raise RuntimeError("BACore.depth_variance: hessian() has not run")
+        if _BACORE_OWNER.get(self.ws.data_ptr(), id(self)) != id(self):
+            raise RuntimeError("BACore.depth_variance: another BACore of the same window shape has linearised into the shared "
+                               "workspace since this object's hessian(); call hessian() again first")
+        _raise_pending_eta_error((self.ws, self.nbytes), self._dims())
+        return _depth_variance(self._dims(), self.ws, self.nbytes, self.lm if lm is None else float(lm),
+                               self.ep if ep is None else float(ep), out, self.poses.device)
+
+
+_DV_SCRATCH = {}     # (device, stream, P) -> (tensor, nbytes): the factor and the inverse of the damped reduced system
+
+
+def _depth_variance(dims, ws, nbytes, lm, ep, out, device):
+    """dba_ba_depth_variance on a workspace that holds a linearised and reduced window"""
+    N, B, ht, wd, t0, t1 = dims
+    if out is None:
+        out = torch.full((B, ht, wd), float("nan"), dtype=torch.float32, device=device)
+    else:
+        _check(out, "out", torch.float32)
+        if out.dim() != 3 or tuple(out.shape[1:]) != (ht, wd) or out.device != ws.device:
+            raise RuntimeError("depth_variance: out must be [>= %d, %d, %d] on %s, got %s" % (B, ht, wd, ws.device, tuple(out.shape)))
+    lib = _lib.load()
+    key = (device, torch.cuda.current_stream().cuda_stream, t1 - t0)
+    ent = _DV_SCRATCH.get(key)
+    if ent is None:
+        need = lib.dba_ba_depth_variance_scratch_bytes(t1 - t0)
+        # (a window the stage does not take: the call itself says which way, before it touches the device)
+        ent = _DV_SCRATCH[key] = (torch.empty(max(need, 8), dtype=torch.uint8, device=device), need)
+    rc = lib.dba_ba_depth_variance(N, B, ht, wd, t0, t1, float(lm), float(ep), _ptr(out), int(out.shape[0]), _ptr(ent[0]), ent[1],
+                                   _ptr(ws), nbytes, _stream())
+    _lib.check(rc, "dba_ba_depth_variance")
+    return out
+
 
 def _check_geom(op, poses, disps, intrinsics, ii=None, jj=None, ix=None, thresh=None, every_frame=True):
     """Shapes the geometry kernels rely on and cannot see (they read poses[index], disps[index] and intrinsics[0..3] unchecked,

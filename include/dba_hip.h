@@ -365,6 +365,31 @@ int dba_bacore_optimize(const double *H_host, const double *v_host, int N, int B
                         int t0, int t1, float lm, float ep, float *dx_out, void *ws, size_t ws_bytes,
                         dba_stream_t stream);
 
+/* Marginal variances of the inverse depths of the window, from the system the last linearisation + reduction on `ws` left
+ * there (csrc/depth_variance.hip).  With E [(P+N), 6, HW] (rows 0..P-1: a frame's own pose; row P + n: edge n, pose jj[n],
+ * depths of frame ii[n]), Q = 1 / C [|kx|, HW] (float32) and the LOWER triangle of H = A - E Q E^T (float64):
+ *     Sd = H + diag(ep + lm diag(H))      -- what dba_ba_solve factorises --,   M = Sd^-1,
+ *     var_out[f, k] = Q[m, k] + Q[m, k]^2 * sum over r, s in rows(f) of  E[r, :, k]^T M[pose(r) block, pose(s) block] E[s, :, k]
+ * for every slot m of kx (f = kx[m]) and pixel k; rows(f) = the rows of E whose depths are frame f's and whose pose lies
+ * inside [t0, t1).  This is the k-th diagonal entry of the depth block of the inverse of [[Sd + E Q E^T, E], [E^T, C]]: the
+ * covariance of the inverse depths given the poses before t0, under the damping of the step.  A frame without such a row gets Q.
+ * All sums in float64, no atomics (bit-identical from run to run), three launches on `stream`, no host synchronisation.
+ *   var_out [out_rows, ht, wd] float32, addressed by frame id like disps; rows of frames outside kx are not written.
+ *   scratch: device memory of dba_ba_depth_variance_scratch_bytes(t1 - t0) bytes (0: P unsupported), aligned to 8; it holds
+ *     the factor, M and a status word -- the workspace does not grow.  Reads the tables of stage 0 (kx, eoff, einfo): no ii, jj.
+ *   A pivot of the factorisation that is not positive is no error code: every written row is NaN (the reference's solve
+ *     degrades silently too).  H, E, Q, dx and meta are not modified; the solvers do not modify H either, so the call is valid
+ *     from the reduction until the next linearisation on `ws`, before or after dba_ba_solve / dba_ba_update / dba_bacore_retract.
+ * Returned BEFORE ANY RUNTIME CALL: DBA_ERR_ARG for a null or misaligned pointer, sizes ba_plan refuses, P < 1 or
+ * out_rows < B; DBA_ERR_UNSUPPORTED for P > 64 or N > 1023; DBA_ERR_WORKSPACE for a workspace or scratch that is too small. */
+size_t dba_ba_depth_variance_scratch_bytes(int P);
+int dba_ba_depth_variance(int N, int B, int ht, int wd, int t0, int t1, float lm, float ep, float *var_out, int out_rows,
+                          void *scratch, size_t scratch_bytes, void *ws, size_t ws_bytes, dba_stream_t stream);
+/* the same, one part at a time (tools/bench_depth_variance.py): parts = 1: M = Sd^-1 into the scratch (two launches), 2: the
+ * quadratic form with the M an earlier call left in THIS scratch (one launch), 3: both; anything else is DBA_ERR_ARG */
+int dba_ba_depth_variance_parts(int N, int B, int ht, int wd, int t0, int t1, float lm, float ep, float *var_out, int out_rows,
+                                void *scratch, size_t scratch_bytes, void *ws, size_t ws_bytes, dba_stream_t stream, int parts);
+
 /* ------------------------------------------------------------------------------------------
  * Correlation volume: CorrBlock (dbaf/modules/corr.py:24-71) and its lookup
  * droid_backends.corr_index_forward (src/droid.cpp:231-239, src/correlation_kernels.cu:19-70,126-155).
