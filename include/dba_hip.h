@@ -448,7 +448,7 @@ int dba_corr_lookup_arm_timing(void *start_event, void *stop_event);
  * correction); larger source maps are not supported. */
 int dba_corr_volume_build_sheared_supported(int C, int h1, int w1, int h2, int w2, int num_levels);
 /* Which kernel dba_corr_volume_build_sheared[_slots] launches for a shape: a pure host decision (the shape, the planes' pixel
- * order and the DBA_BUILD_KERNEL / DBA_BUILD_OPERANDS / DBA_BUILD_WAVES / DBA_BUILD_G16_GENERIC switches, each read once per
+ * order and the DBA_BUILD_KERNEL / DBA_BUILD_OPERANDS / DBA_BUILD_WAVES switches, each read once per
  * process); nothing is launched.  The launcher switches on the same value. */
 enum dba_corr_build_route {
   DBA_CORR_ROUTE_UNFUSED = 0,       /* not supported: dba_corr_volume_build + dba_corr_shear_level */

@@ -68,5 +68,5 @@ python $REPO/scratch/hbm_ceiling.py > $OUT/${TAG}_hbm_ceiling.txt 2>&1
   [ -x $REPO/scratch/bin/mfma_f64_lat ] && echo "--- scratch/mfma_f64_lat.hip" && timeout 60 $REPO/scratch/bin/mfma_f64_lat 2>&1 | grep "cycles per link"
   [ -x $REPO/scratch/bin/solve_prof ] && echo "--- register-tile / skyline kernels (scratch/solve_tile_test.hip)" && (HARNESS_BAND=1 timeout 120 $REPO/scratch/bin/solve_prof; timeout 120 $REPO/scratch/bin/solve_prof) 2>&1 | grep -A3 "n=144 band= 24 spd=1\|n=186\|n=378 band= 36"
 } > $OUT/${TAG}_solver_stages.txt
-timeout 120 python $REPO/scratch/build_ab.py $TAG > $OUT/${TAG}_build_shapes.txt 2>&1
+timeout 600 python $REPO/tools/bench_corr_build.py $REPO/dba-fusion_amd/lib/libdba_hip.so --labels $TAG --repeats 3 --shapes 64x64,28x107,55x55,48x64 > $OUT/${TAG}_build_shapes.txt 2>&1
 ls -la $OUT | grep ${TAG}_ | head -50
