@@ -21,7 +21,7 @@ from dbaf_amd._lib import DBA_F16, DBA_F32
 
 __all__ = ["ba", "ba_extend", "frame_distance", "projmap", "depth_filter", "iproj", "altcorr_forward",
            "altcorr_backward", "corr_index_forward", "corr_index_backward", "BACore", "ba_clamped", "gather_edges",
-           "check_async_errors"]
+           "check_async_errors", "ba_cost"]
 
 # The compiled adapter (csrc_ext/droid_backends_ext.cpp -> _droid_backends_C.so, `make ext`): the pybind11 module a
 # maintainer would build in place of the reference's src/droid.cpp -- every binding of droid.cpp:297-316 over the same C ABI.
@@ -553,6 +553,15 @@ class BACore:
         return _depth_variance(self._dims(), self.ws, self.nbytes, self.lm if lm is None else float(lm),
                                self.ep if ep is None else float(ep), out, self.poses.device)
 
+    def cost(self, out=None):
+        """The cost report of the window on the tensors init() cached, as they are NOW: float64 [N + 1, 4] (cost, wsum, n_used,
+        r2max per edge, the total in row N; `ba_cost`).  Not a reference binding.  Valid any time after init(): it reads neither
+        the workspace nor the linearisation, so hessian -> cost -> retract leaves the state hessian -> retract leaves, and a
+        call before and one after retract() say whether the step lowered the objective.  Two launches, no host
+        synchronisation."""
+        assert self._ready, "BACore.init must be called first"
+        return ba_cost(self.poses, self.disps, self.intrinsics, self.targets, self.weights, self.ii, self.jj, out=out)
+
 
 _DV_SCRATCH = {}     # (device, stream, P) -> (tensor, nbytes): the factor and the inverse of the damped reduced system
 
@@ -576,6 +585,55 @@ def _depth_variance(dims, ws, nbytes, lm, ep, out, device):
     rc = lib.dba_ba_depth_variance(N, B, ht, wd, t0, t1, float(lm), float(ep), _ptr(out), int(out.shape[0]), _ptr(ent[0]), ent[1],
                                    _ptr(ws), nbytes, _stream())
     _lib.check(rc, "dba_ba_depth_variance")
+    return out
+
+
+_COST_SCRATCH = {}   # (device, stream, N, ht, wd) -> (tensor, nbytes): one entry of four doubles per (edge, pixel slice)
+
+
+def ba_cost(poses, disps, intrinsics, targets, weights, ii, jj, out=None):
+    """The objective of `ba` per edge: float64 [N + 1, 4] on the device, row n = (cost, wsum, n_used, r2max) of edge n over its
+    used pixels, row N the window's total (dba_ba_cost, include/dba_hip.h; dbaf_amd.ba_report names the columns and derives
+    rms_px and worst_edges).  It is the cost of ba_linearize_kernel -- the z < 0.25 cut, w = 0.001 x weight, the relative pose
+    in float64 rounded once -- not that of the torch reprojection.  Not a reference binding.  Arguments as `ba` takes them
+    (without disps_sens and eta, which the residuals do not depend on); `out`: float64 [>= N + 1, 4], written in place, rows
+    beyond N + 1 untouched.  An edge whose ii or jj is outside [0, B) reads (NaN, NaN, -1, NaN).  Two launches on the current
+    stream, no atomics, no host synchronisation; the scratch is kept per (device, stream, N, ht, wd)."""
+    for x, nm, dt in ((poses, "poses", torch.float32), (disps, "disps", torch.float32), (intrinsics, "intrinsics", torch.float32),
+                      (targets, "targets", torch.float32), (weights, "weights", torch.float32), (ii, "ii", torch.int64),
+                      (jj, "jj", torch.int64)):
+        _check(x, nm, dt)
+    if disps.dim() != 3:
+        raise RuntimeError("ba_cost: disps must be [B, ht, wd], got %s" % (tuple(disps.shape),))
+    B, ht, wd = (int(x) for x in disps.shape)
+    N = int(ii.shape[0])
+    if ii.dim() != 1 or jj.shape != ii.shape:
+        raise RuntimeError("ba_cost: ii and jj must be 1-D and of one shape, got %s and %s" % (tuple(ii.shape), tuple(jj.shape)))
+    if poses.numel() < 7 * B or intrinsics.numel() < 4:
+        raise RuntimeError("ba_cost: poses must hold 7 values for each of the %d frames of disps, intrinsics (fx, fy, cx, cy)" % B)
+    if targets.numel() != N * 2 * ht * wd or weights.numel() != N * 2 * ht * wd:
+        raise RuntimeError("ba_cost: targets and weights must be [%d, 2, %d, %d], got %s and %s"
+                           % (N, ht, wd, tuple(targets.shape), tuple(weights.shape)))
+    dev = disps.device
+    if any(x.device != dev for x in (poses, intrinsics, targets, weights, ii, jj)):
+        raise RuntimeError("ba_cost: all tensors must live on one device")
+    if out is None:
+        out = torch.empty(N + 1, 4, dtype=torch.float64, device=dev)      # (every entry is written)
+    else:
+        _check(out, "out", torch.float64)
+        if out.dim() != 2 or out.shape[1] != 4 or out.shape[0] < N + 1 or out.device != dev:
+            raise RuntimeError("ba_cost: out must be float64 [>= %d, 4] on %s, got %s" % (N + 1, dev, tuple(out.shape)))
+    lib = _lib.load()
+    key = (dev, torch.cuda.current_stream().cuda_stream, N, ht, wd)
+    ent = _COST_SCRATCH.get(key)
+    if ent is None:
+        if len(_COST_SCRATCH) >= 8:                   # window shapes change with the graph: keep the latest few
+            _COST_SCRATCH.pop(next(iter(_COST_SCRATCH)))
+        need = lib.dba_ba_cost_scratch_bytes(N, ht, wd)
+        ent = _COST_SCRATCH[key] = (torch.empty(max(need, 16), dtype=torch.uint8, device=dev), need)
+    rc = lib.dba_ba_cost(_ptr(poses), _ptr(disps), _ptr(intrinsics), _ptr(targets), _ptr(weights), _ptr(ii), _ptr(jj), N, B, ht, wd,
+                         _ptr(out), int(out.shape[0]), _ptr(ent[0]), ent[1], _stream())
+    _lib.check(rc, "dba_ba_cost")
     return out
 
 

@@ -390,6 +390,28 @@ int dba_ba_depth_variance(int N, int B, int ht, int wd, int t0, int t1, float lm
 int dba_ba_depth_variance_parts(int N, int B, int ht, int wd, int t0, int t1, float lm, float ep, float *var_out, int out_rows,
                                 void *scratch, size_t scratch_bytes, void *ws, size_t ws_bytes, dba_stream_t stream, int parts);
 
+/* The BA cost report (csrc/ba_cost.hip): what the linearisation minimises, per edge.  For edge n with i = ii[n], j = jj[n] and
+ * pixel k = v * wd + u: Gij = Tj Ti^-1 (i == j: the fixed stereo baseline t = (-0.1, 0, 0), q = identity) formed in float64
+ * and rounded once, X = ((u - cx) / fx, (v - cy) / fy, 1), d = disps[i, k], (x, y, z) = R X + d t.  A pixel with z < 0.25 is
+ * cut.  Otherwise r_u = targets[n, 0, k] - (fx x / z + cx), r_v = targets[n, 1, k] - (fy y / z + cy), w_u = 0.001 weights[n, 0, k],
+ * w_v = 0.001 weights[n, 1, k] -- the float32 expressions of ba_linearize_kernel; a stereo edge keeps its weights (the residual
+ * its depth block sees).  A pixel is used if it is not cut and w_u + w_v != 0.  Over the used pixels of the edge, in float64:
+ *     out[n] = (cost = sum w_u r_u^2 + w_v r_v^2,  wsum = sum w_u + w_v,  n_used = their number,  r2max = max r_u^2 + r_v^2),
+ * (0, 0, 0, 0) without a used pixel; out[N] = the sums of cost, wsum, n_used and the max of r2max over the rows as stored.
+ *   out [out_rows >= N + 1, 4] float64 on the device; rows beyond N are not written.
+ *   scratch: dba_ba_cost_scratch_bytes(N, ht, wd) = 32 N ceil(ht wd / 1024) bytes of device memory, aligned to 16 (0 for N == 0
+ *     and for sizes the call refuses); four doubles per (edge, slice of 1024 pixels).  No BA workspace is needed or touched.
+ *   A NaN among a used pixel's inputs makes that edge's cost and r2max NaN, and the total's; no other row changes.  An edge
+ *   whose ii or jj lies outside [0, B) reads (NaN, NaN, -1, NaN) and nothing is read through the index.
+ * Two launches on `stream` (N == 0: one, which writes a zero total row), no atomics -- the same bytes from run to run and from
+ * device to device --, no host synchronisation.  Returned BEFORE ANY RUNTIME CALL: DBA_ERR_ARG for a null or misaligned pointer
+ * (N == 0 needs `out` alone), N < 0, B < 1, ht or wd < 1, out_rows < N + 1; DBA_ERR_UNSUPPORTED when N ceil(ht wd / 1024) or
+ * ht wd exceeds 2^31 - 1; DBA_ERR_WORKSPACE for a scratch that is too small. */
+size_t dba_ba_cost_scratch_bytes(int N, int ht, int wd);
+int dba_ba_cost(const float *poses, const float *disps, const float *intrinsics4, const float *targets, const float *weights,
+                const int64_t *ii, const int64_t *jj, int N, int B, int ht, int wd, double *out, int out_rows, void *scratch,
+                size_t scratch_bytes, dba_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Correlation volume: CorrBlock (dbaf/modules/corr.py:24-71) and its lookup
  * droid_backends.corr_index_forward (src/droid.cpp:231-239, src/correlation_kernels.cu:19-70,126-155).
