@@ -16,7 +16,7 @@
 // and meta only.  E and Q are written by the linearisation alone.  So the stage gives the same result before and after
 // dba_ba_solve, dba_ba_update and BACore.retract, until the next linearisation on the workspace.  It leaves meta[1] alone.
 //
-// Three launches:
+// Three launches (the first and the column solve of the second live in reduced_inverse.h, which pose_covariance.hip shares):
 //   1. dv_factor_kernel, ONE workgroup: Sd = L L^T, left-looking by panels of DV_NB columns.  n <= DV_RESIDENT_MAX: the
 //      triangle stays in LDS for the whole factorisation.  Beyond: one panel [n - k0][DV_NB] in LDS at a time, the finished
 //      panels are read back from the scratch (L2).  L leaves as a full square (L below, L^T above the diagonal), so that both
@@ -30,112 +30,19 @@
 //      four partial sums are added in wave order.  One float store per pixel into var_out[kx[m]].
 // The general solver (ba_solve_general.inc) is not reused: it keeps a packed triangle with the right-hand side as an extra row,
 // in LDS or in the workspace's own scratch, and hands out dx -- the inverse needs L itself, as rows AND as columns.
-#include "ba_kernels.h"
+#include "reduced_inverse.h"   // the factor kernel, one column of the inverse, the scratch: shared with pose_covariance.hip
 
 namespace dba {
 namespace {
 
-constexpr int DV_MAX_P = 64;
-constexpr int DV_THREADS = 256;
-constexpr int DV_NB = 32;              // columns of a Cholesky panel
-constexpr int DV_RESIDENT_MAX = 128;   // unknowns up to which the whole triangle lives in LDS
 constexpr int DV_TP = 64;              // pixels of a quadratic-form workgroup: one per lane
 constexpr int DV_RT = 8;               // rows of a tile of staged blocks of M
 constexpr int DV_RCAP = 24;            // rows of E a workgroup stages in LDS
 constexpr int DV_RLIST = 1024;         // rows of one frame at the most (its own + N out-edges)
 
-constexpr size_t DV_STATUS_BYTES = 256;
-
-__host__ __device__ inline int dv_ld(int n) { return n | 1; }   // odd row length of the resident triangle: no bank column
-inline size_t dv_scratch_bytes(int n) { return 2 * sizeof(double) * (size_t)n * n + DV_STATUS_BYTES; }
-inline size_t dv_factor_lds(int n) {
-  const size_t doubles = n <= DV_RESIDENT_MAX ? (size_t)n * dv_ld(n) : (size_t)n * (DV_NB + 1);
-  return sizeof(double) * doubles + 16;
-}
 constexpr size_t DV_QUAD_LDS = sizeof(double) * (DV_RT * DV_RT * 36 + 4 * DV_TP) + sizeof(float) * DV_RCAP * 6 * DV_TP +
                                sizeof(int) * DV_RLIST + 16;
 static_assert(DV_QUAD_LDS <= 64 * 1024, "the quadratic form stays inside the default dynamic LDS limit");
-
-__device__ __forceinline__ double dv_wave_sum(double s) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
-  return s;
-}
-
-__global__ __launch_bounds__(DV_THREADS) void dv_factor_kernel(const double *__restrict__ H, int n, double lm, double ep,
-                                                               double *__restrict__ Lg, int *__restrict__ status) {
-  extern __shared__ __attribute__((aligned(16))) double dv_sm[];
-  const int tid = threadIdx.x, nt = blockDim.x;
-  const bool resident = n <= DV_RESIDENT_MAX;
-  const int ld = resident ? dv_ld(n) : n;          // row length of the finished factor: in LDS, or in the scratch
-  double *Lf = resident ? dv_sm : Lg;
-  int *bad = reinterpret_cast<int *>(dv_sm + (resident ? (size_t)n * dv_ld(n) : (size_t)n * (DV_NB + 1)));
-  auto damped = [&](int i, int j) {                // j <= i: the lower triangle of H is all that is read
-    double v = H[(size_t)i * n + j];
-    if (i == j) v += ep + lm * v;
-    return v;
-  };
-  if (tid == 0) *bad = 0;
-  if (resident) {
-    for (int e = tid; e < n * n; e += nt) {
-      const int i = e / n, j = e - i * n;
-      if (j <= i) Lf[i * ld + j] = damped(i, j);
-    }
-  }
-  __syncthreads();
-
-  for (int k0 = 0; k0 < n; k0 += DV_NB) {
-    const int kb = min(DV_NB, n - k0), rows = n - k0;
-    double *Pn = resident ? dv_sm + (size_t)k0 * ld + k0 : dv_sm;   // entry (r, j) of the panel: row k0 + r, column k0 + j
-    const int ldp = resident ? ld : DV_NB + 1;
-    // the panel minus what the finished columns contribute
-    for (int e = tid; e < rows * kb; e += nt) {
-      const int r = e / kb, j = e - r * kb;
-      if (j > r) continue;
-      double a = resident ? Pn[r * ldp + j] : damped(k0 + r, k0 + j);
-      const double *x = Lf + (size_t)(k0 + r) * ld, *y = Lf + (size_t)(k0 + j) * ld;
-      for (int t = 0; t < k0; t++) a = fma(-x[t], y[t], a);
-      Pn[r * ldp + j] = a;
-    }
-    __syncthreads();
-    // its columns, one by one: scale, then take the column out of the ones to its right
-    for (int j = 0; j < kb; j++) {
-      const double d = Pn[j * ldp + j];
-      const bool ok = d > 0.0;                     // (false for a NaN too)
-      if (!ok && tid == 0) *bad = 1;
-      const double piv = sqrt(ok ? d : 1.0);
-      for (int r = j + 1 + tid; r < rows; r += nt) Pn[r * ldp + j] /= piv;
-      __syncthreads();                             // every thread has read d
-      if (tid == 0) Pn[j * ldp + j] = piv;
-      const int nc = kb - 1 - j;
-      for (int e = tid; e < (rows - j - 1) * nc; e += nt) {
-        const int r = j + 1 + e / nc, c = j + 1 + e % nc;
-        if (c <= r) Pn[r * ldp + c] = fma(-Pn[r * ldp + j], Pn[c * ldp + j], Pn[r * ldp + c]);
-      }
-      __syncthreads();
-    }
-    if (!resident) {
-      for (int e = tid; e < rows * kb; e += nt) {
-        const int r = e / kb, j = e - r * kb;
-        if (j > r) continue;
-        const double v = Pn[r * ldp + j];
-        Lg[(size_t)(k0 + r) * n + k0 + j] = v;
-        Lg[(size_t)(k0 + j) * n + k0 + r] = v;
-      }
-      __syncthreads();
-    }
-  }
-  if (resident) {
-    for (int e = tid; e < n * n; e += nt) {
-      const int i = e / n, j = e - i * n;
-      if (j > i) continue;
-      const double v = Lf[i * ld + j];
-      Lg[(size_t)i * n + j] = v;
-      Lg[(size_t)j * n + i] = v;
-    }
-  }
-  if (tid == 0) status[0] = *bad;
-}
 
 __global__ __launch_bounds__(DV_THREADS) void dv_inverse_kernel(const double *__restrict__ Lg, int n,
                                                                 double *__restrict__ Mg, const int *__restrict__ status) {
@@ -144,22 +51,7 @@ __global__ __launch_bounds__(DV_THREADS) void dv_inverse_kernel(const double *__
   const int c = blockIdx.x * (DV_THREADS / 64) + wave;
   if (c >= n || status[0]) return;                 // (no workgroup barrier below)
   double *y = dv_sm + (size_t)wave * n;            // lane t & 63 owns y[t]
-  for (int t = lane; t < n; t += 64) y[t] = 0.0;
-  const int tb = c & ~63;
-  for (int i = c; i < n; i++) {
-    const double *row = Lg + (size_t)i * n;
-    double s = 0.0;
-    for (int t = tb + lane; t < i; t += 64) s = fma(row[t], y[t], s);
-    s = dv_wave_sum(s);
-    if ((i & 63) == lane) y[i] = ((i == c ? 1.0 : 0.0) - s) / row[i];
-  }
-  for (int i = n - 1; i >= 0; i--) {
-    const double *row = Lg + (size_t)i * n;        // above the diagonal: L^T
-    double s = 0.0;
-    for (int t = i + 1 + ((lane - (i + 1)) & 63); t < n; t += 64) s = fma(row[t], y[t], s);
-    s = dv_wave_sum(s);
-    if ((i & 63) == lane) y[i] = (y[i] - s) / row[i];
-  }
+  dv_solve_column(Lg, n, c, y, lane);
   for (int t = lane; t < n; t += 64) Mg[(size_t)c * n + t] = y[t];
 }
 
@@ -292,20 +184,12 @@ int dba_ba_depth_variance_parts(int N, int B, int ht, int wd, int t0, int t1, fl
   const int n = 6 * plan.P;
   if (scratch_bytes < dv_scratch_bytes(n)) return DBA_ERR_WORKSPACE;
 
-  double *Lg = static_cast<double *>(scratch);
-  double *Mg = Lg + (size_t)n * n;
-  int *status = reinterpret_cast<int *>(Mg + (size_t)n * n);
+  const DvScratch sc(scratch, n);
+  double *Lg = sc.Lg, *Mg = sc.Mg;
+  int *status = sc.status;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  static DeviceOnce once;
-  if (once.needed()) {
-    DBA_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&dv_factor_kernel),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)dv_factor_lds(DV_RESIDENT_MAX)));
-    once.done();
-  }
   if (parts & 1) {
-    hipLaunchKernelGGL(dv_factor_kernel, dim3(1), dim3(DV_THREADS), dv_factor_lds(n), s, plan.W.H, n, (double)lm, (double)ep, Lg,
-                       status);
-    DBA_LAUNCH_CHECK();
+    if (const int rc = dv_launch_factor(plan.W.H, n, lm, ep, sc, s)) return rc;
     constexpr int per = DV_THREADS / 64;
     hipLaunchKernelGGL(dv_inverse_kernel, dim3((n + per - 1) / per), dim3(DV_THREADS), sizeof(double) * per * n, s, Lg, n, Mg,
                        status);

@@ -124,6 +124,8 @@ SYMBOLS = {
     "dba_ba_depth_variance_scratch_bytes": (c_size_t, [c_int]),
     "dba_ba_depth_variance": (c_int, [c_int] * 6 + [c_float, c_float, _P, c_int, _P, c_size_t, _P, c_size_t, _P]),
     "dba_ba_depth_variance_parts": (c_int, [c_int] * 6 + [c_float, c_float, _P, c_int, _P, c_size_t, _P, c_size_t, _P, c_int]),
+    "dba_ba_pose_covariance": (c_int, [_P] + [c_int] * 6 + [c_float, c_float, _P, c_int, _P, c_int, _P, _P, c_int, _P, c_int,
+                                       _P, c_size_t, _P, c_size_t, _P]),
     "dba_ba_cost_scratch_bytes": (c_size_t, [c_int] * 3),
     "dba_ba_cost": (c_int, [_P] * 7 + [c_int] * 4 + [_P, c_int, _P, c_size_t, _P]),
     "dba_corr_index_forward": (c_int, [_P, _P, _P] + [c_int] * 7 + [_P]),

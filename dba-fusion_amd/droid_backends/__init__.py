@@ -553,6 +553,61 @@ class BACore:
         return _depth_variance(self._dims(), self.ws, self.nbytes, self.lm if lm is None else float(lm),
                                self.ep if ep is None else float(ep), out, self.poses.device)
 
+    def pose_covariance(self, poses=None, pairs=None, Tbc=None, out=None, lm=None, ep=None):
+        """6 x 6 covariances of the window's poses from the system the last hessian() / hessian_gtsam() left in the workspace
+        (dba_ba_pose_covariance, include/dba_hip.h): the blocks of (H + damping)^-1, in float64 -- the covariance of a pose's
+        tangent (tau, phi; T' = Exp(xi) T) given the fixed poses before t0, the depths marginalised out.
+        Not a reference binding.
+          poses: frame indices in [t0, t1), any order, repeats allowed, at most 64; default: every window pose t0 .. t1 - 1.
+          pairs: (a, b) frame pairs, at most 64: the covariance of the relative pose T_b T_a^-1 (xi_rel = xi_b - Ad xi_a), with
+                 Ad from the poses as they are stored when the call runs; a frame outside [t0, t1) is a fixed pose.
+          Tbc:   a gtsam.Pose3, a 4x4 matrix, a (t, q) 7-vector or the 6x6 block of hessian_gtsam: the marginal blocks come in
+                 the tangent coordinates BA2GTSAM hands to the factor graph (A^-1 S A^-T, dx_ba = A dx_g).  Relative blocks
+                 are ALWAYS in camera tangents.
+        Returns a float64 device tensor [len(poses), 6, 6]; with `pairs` the tuple (that, [len(pairs), 6, 6]).  `out`: the
+        tensor (or the tuple of two) to write into, [>= jobs, 6, 6] float64; rows beyond the jobs keep what they had.  Every
+        block is symmetric to the bit; a system that cannot be factorised gives NaN.  Valid from hessian() until the next
+        one, before or after retract().  lm / ep default to init's.  Two launches, no host synchronisation."""
+        assert self._ready, "BACore.init must be called first"
+        if self._linearised is None:
+            raise RuntimeError("BACore.pose_covariance: hessian() has not run")
+        if _BACORE_OWNER.get(self.ws.data_ptr(), id(self)) != id(self):
+            raise RuntimeError("BACore.pose_covariance: another BACore of the same window shape has linearised into the shared "
+                               "workspace since this object's hessian(); call hessian() again first")
+        _raise_pending_eta_error((self.ws, self.nbytes), self._dims())
+        marg = list(range(self.t0, self.t1)) if poses is None else [int(f) for f in poses]
+        pr = [] if pairs is None else [(int(a), int(b)) for a, b in pairs]
+        dev = self.poses.device
+        if poses is not None and any(f < self.t0 or f >= self.t1 for f in marg):
+            raise RuntimeError("BACore.pose_covariance: poses must lie in the window [%d, %d)" % (self.t0, self.t1))
+        if pr and self.poses.numel() < 7 * self.B:
+            raise RuntimeError("BACore.pose_covariance: poses must hold 7 values for each of the %d frames" % self.B)
+        outs = list(out) if isinstance(out, (tuple, list)) else [out, None]
+        for k, (cnt, nm) in enumerate(((len(marg), "out"), (len(pr), "out[1]"))):
+            if outs[k] is None:
+                outs[k] = torch.empty(cnt, 6, 6, dtype=torch.float64, device=dev)      # (every block is written)
+            else:
+                _check(outs[k], nm, torch.float64)
+                if outs[k].dim() != 3 or tuple(outs[k].shape[1:]) != (6, 6) or outs[k].shape[0] < cnt or outs[k].device != dev:
+                    raise RuntimeError("BACore.pose_covariance: %s must be float64 [>= %d, 6, 6] on %s, got %s"
+                                       % (nm, cnt, dev, tuple(outs[k].shape)))
+        ainv = None
+        if Tbc is not None:
+            import numpy as _np
+            from dbaf_amd import fusion
+            A = _np.asarray(Tbc, _np.float64) if (not hasattr(Tbc, "matrix") and _np.shape(Tbc) == (6, 6)) else fusion.tangent_block(Tbc)
+            ainv = (ctypes.c_double * 36)(*_np.linalg.inv(A).reshape(-1))
+        cm = (ctypes.c_int * max(len(marg), 1))(*marg)
+        cp = (ctypes.c_int * max(2 * len(pr), 1))(*[f for ab in pr for f in ab])
+        ent = _dv_scratch(dev, self.P)
+        rc = _lib.load().dba_ba_pose_covariance(
+            _ptr(self.poses), *self._dims(), self.lm if lm is None else float(lm), self.ep if ep is None else float(ep),
+            ctypes.cast(cm, ctypes.c_void_p), len(marg), ctypes.cast(cp, ctypes.c_void_p), len(pr),
+            None if ainv is None else ctypes.cast(ainv, ctypes.c_void_p), _ptr(outs[0]), int(outs[0].shape[0]), _ptr(outs[1]),
+            int(outs[1].shape[0]), _ptr(ent[0]), ent[1], _ptr(self.ws), self.nbytes, _stream())
+        _lib.check(rc, "dba_ba_pose_covariance")
+        return outs[0] if pairs is None else (outs[0], outs[1])
+
     def cost(self, out=None):
         """The cost report of the window on the tensors init() cached, as they are NOW: float64 [N + 1, 4] (cost, wsum, n_used,
         r2max per edge, the total in row N; `ba_cost`).  Not a reference binding.  Valid any time after init(): it reads neither
@@ -566,6 +621,17 @@ class BACore:
 _DV_SCRATCH = {}     # (device, stream, P) -> (tensor, nbytes): the factor and the inverse of the damped reduced system
 
 
+def _dv_scratch(device, P):
+    """the scratch of depth_variance and pose_covariance for a window of P poses on the current stream"""
+    key = (device, torch.cuda.current_stream().cuda_stream, P)
+    ent = _DV_SCRATCH.get(key)
+    if ent is None:
+        need = _lib.load().dba_ba_depth_variance_scratch_bytes(P)
+        # (a window the stage does not take: the call itself says which way, before it touches the device)
+        ent = _DV_SCRATCH[key] = (torch.empty(max(need, 8), dtype=torch.uint8, device=device), need)
+    return ent
+
+
 def _depth_variance(dims, ws, nbytes, lm, ep, out, device):
     """dba_ba_depth_variance on a workspace that holds a linearised and reduced window"""
     N, B, ht, wd, t0, t1 = dims
@@ -576,12 +642,7 @@ def _depth_variance(dims, ws, nbytes, lm, ep, out, device):
         if out.dim() != 3 or tuple(out.shape[1:]) != (ht, wd) or out.device != ws.device:
             raise RuntimeError("depth_variance: out must be [>= %d, %d, %d] on %s, got %s" % (B, ht, wd, ws.device, tuple(out.shape)))
     lib = _lib.load()
-    key = (device, torch.cuda.current_stream().cuda_stream, t1 - t0)
-    ent = _DV_SCRATCH.get(key)
-    if ent is None:
-        need = lib.dba_ba_depth_variance_scratch_bytes(t1 - t0)
-        # (a window the stage does not take: the call itself says which way, before it touches the device)
-        ent = _DV_SCRATCH[key] = (torch.empty(max(need, 8), dtype=torch.uint8, device=device), need)
+    ent = _dv_scratch(device, t1 - t0)
     rc = lib.dba_ba_depth_variance(N, B, ht, wd, t0, t1, float(lm), float(ep), _ptr(out), int(out.shape[0]), _ptr(ent[0]), ent[1],
                                    _ptr(ws), nbytes, _stream())
     _lib.check(rc, "dba_ba_depth_variance")

@@ -390,6 +390,38 @@ int dba_ba_depth_variance(int N, int B, int ht, int wd, int t0, int t1, float lm
 int dba_ba_depth_variance_parts(int N, int B, int ht, int wd, int t0, int t1, float lm, float ep, float *var_out, int out_rows,
                                 void *scratch, size_t scratch_bytes, void *ws, size_t ws_bytes, dba_stream_t stream, int parts);
 
+/* 6 x 6 covariances of the window's poses, from the system the last linearisation + reduction on `ws` left there
+ * (csrc/pose_covariance.hip; the factor and the column solve are those of dba_ba_depth_variance, csrc/reduced_inverse.h).  With
+ *     Sd = H + diag(ep + lm diag(H)),   M = Sd^-1   (H: the LOWER triangle, float64)
+ * the blocks of M are the covariances of the pose tangents given the gauge -- the poses outside [t0, t1), which BA keeps fixed --
+ * with the depths marginalised out, under the damping of the step.  Tangents are this library's: (tau, phi), applied on the left
+ * of the world -> camera pose, T' = Exp(xi) T.
+ *   marginal job k:  out_marg[k] = S_bb = M[6p:6p+6, 6p:6p+6], p = marg[k] - t0.  With Ainv (6 x 6 row-major, HOST, may be NULL)
+ *       out_marg[k] = Ainv S_bb Ainv^T: with Ainv = A^-1, A the block of dba_bacore_hessian_host's layout 1 (dx_ba = A dx_g), the
+ *       covariance in the factor-graph side's tangent coordinates.  Ainv applies to marginal jobs ONLY.
+ *   relative job k = (a, b) = (pairs[2k], pairs[2k+1]):  with G = T_b T_a^-1 = (R, t) and Ad = Ad(G) = [[R, [t]x R], [0, R]],
+ *       out_pairs[k] = S_bb + Ad S_aa Ad^T - Ad S_ab - S_ba Ad^T,
+ *       the first-order covariance of xi_rel in G' = Exp(xi_rel) G, xi_rel = xi_b - Ad xi_a: ALWAYS in camera tangents.  A frame
+ *       outside [t0, t1) is a fixed pose, its blocks of S are zero: (a < t0, b) gives S_bb.  Ad is formed in float64 from
+ *       `poses` [B, 7] (t, q_xyzw; q normalised in float64) as stored when the kernel runs.
+ *   marg [n_marg], pairs [2 n_pairs]: HOST arrays of frame indices; they and Ainv are consumed before the call returns (they
+ *   travel in the kernel's argument block: no copy, no host synchronisation, the call records into a hipGraph).
+ *   out_marg [out_marg_rows >= n_marg, 6, 6], out_pairs [out_pair_rows >= n_pairs, 6, 6]: float64, device; rows beyond the job
+ *   count are not written.  Every block is written from its lower triangle and mirrored: symmetric to the bit.  Without Ainv a
+ *   marginal block holds the bits dba_ba_depth_variance_parts(parts = 1) leaves in the lower triangle of that block of M.
+ *   scratch: as for dba_ba_depth_variance (the same size, the same layout; the M part is not touched).
+ * All arithmetic in float64, no atomics (bit-identical from run to run), two launches on `stream`: the factor, then one
+ * workgroup per job.  A pivot that is not positive is no error code: every block is NaN.  Nothing in the workspace is modified
+ * (meta[1] included); valid from the reduction until the next linearisation on `ws`, before or after a solve or a retraction.
+ * Returned BEFORE ANY RUNTIME CALL: DBA_ERR_ARG for a null or misaligned pointer (poses, pairs, out_pairs only with n_pairs > 0;
+ * marg, out_marg only with n_marg > 0), no job at all, more than 64 marginal jobs or 64 pairs, an output with fewer rows than
+ * jobs, a frame index outside [0, B), a marginal index outside [t0, t1), a pair with a == b, sizes ba_plan refuses, P < 1;
+ * DBA_ERR_UNSUPPORTED for P > 64; DBA_ERR_WORKSPACE for a workspace or scratch that is too small. */
+int dba_ba_pose_covariance(const float *poses, int N, int B, int ht, int wd, int t0, int t1, float lm, float ep, const int *marg,
+                           int n_marg, const int *pairs, int n_pairs, const double *Ainv, double *out_marg, int out_marg_rows,
+                           double *out_pairs, int out_pair_rows, void *scratch, size_t scratch_bytes, void *ws, size_t ws_bytes,
+                           dba_stream_t stream);
+
 /* The BA cost report (csrc/ba_cost.hip): what the linearisation minimises, per edge.  For edge n with i = ii[n], j = jj[n] and
  * pixel k = v * wd + u: Gij = Tj Ti^-1 (i == j: the fixed stereo baseline t = (-0.1, 0, 0), q = identity) formed in float64
  * and rounded once, X = ((u - cx) / fx, (v - cy) / fy, 1), d = disps[i, k], (x, y, z) = R X + d t.  A pixel with z < 0.25 is
