@@ -379,13 +379,29 @@ static int ba_solve_stage(const BaPlan &plan, float lm, float ep, const int *fpo
 
 static int ba_update_launch(const BaPlan &plan, float *poses, float *disps, const int64_t *jj, const uint8_t *frame_owned,
                             int update_poses, int update_disps, float *dz_out, float *dx_out, hipStream_t stream,
-                            const float *poses_src = nullptr, float disp_floor = 0.f) {
+                            const float *poses_src = nullptr, float disp_floor = 0.f, const int *skip = nullptr) {
   // (disp_floor > 0: one more block row per frame of the buffer, which clamp the frames this launch does not update)
   dim3 grid((plan.HW + 255) / 256, plan.T.Mmax + 1 + (disp_floor > 0.f ? plan.B : 0));
   hipLaunchKernelGGL(ba_update_kernel, grid, dim3(256), 0, stream, poses, poses_src, disps, jj, frame_owned, plan.HW, plan.t0,
-                     plan.P, update_poses, update_disps, dz_out, dx_out, plan.T, plan.W, disp_floor);
+                     plan.P, update_poses, update_disps, dz_out, dx_out, plan.T, plan.W, disp_floor, skip);
   DBA_LAUNCH_CHECK();
   return DBA_OK;
+}
+
+// the increment of dba_bacore_retract_device: float64 in device memory -> the workspace's float32 slot (:1929-1930)
+__global__ void ba_dx_from_device_kernel(const double *__restrict__ src, float *__restrict__ dx, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) dx[i] = (float)src[i];
+}
+
+int ba_retract_device(const BaPlan &plan, float *poses, float *disps, const int64_t *jj, const double *dx_dev, const int *skip_dev,
+                      float *dx_out, float *dz_out, hipStream_t stream) {
+  const int n = 6 * plan.P;
+  if (n > 0) {
+    hipLaunchKernelGGL(ba_dx_from_device_kernel, dim3((n + 127) / 128), dim3(128), 0, stream, dx_dev, plan.W.dx, n);
+    DBA_LAUNCH_CHECK();
+  }
+  return ba_update_launch(plan, poses, disps, jj, nullptr, 1, 1, dz_out, dx_out, stream, nullptr, 0.f, skip_dev);
 }
 
 // A keyed call (prepared = 2) whose stage 0 rides in its first linearisation (ba_linearize_kernel<.., TF = true>) instead of
@@ -870,6 +886,15 @@ int dba_bacore_retract(float *poses, float *disps, const int64_t *ii, const int6
     DBA_LAUNCH_CHECK();
   }
   return DBA_OK;
+}
+
+int dba_bacore_retract_device(float *poses, float *disps, const int64_t *ii, const int64_t *jj, int N, int B, int ht, int wd, int t0,
+                              int t1, const double *dx_dev, const int *skip_dev, float *dx_out, float *dz_out, void *ws,
+                              size_t ws_bytes, dba_stream_t stream) {
+  (void)ii;
+  if (!dx_dev || !poses || !disps || !jj) return DBA_ERR_ARG;
+  DBA_PLAN_OR_RETURN(plan);
+  return ba_retract_device(plan, poses, disps, jj, dx_dev, skip_dev, dx_out, dz_out, (hipStream_t)stream);
 }
 
 int dba_bacore_optimize(const double *H_host, const double *v_host, int N, int B, int ht, int wd, int t0,

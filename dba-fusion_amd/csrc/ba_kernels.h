@@ -132,8 +132,11 @@ __global__ void ba_schur_gram_kernel(const int64_t *ii, const int64_t *jj, const
                                      int t0, int P, int nch, int lower, BaTables T, BaBuffers W);
 __global__ void ba_update_kernel(float *poses, const float *poses_src, float *disps, const int64_t *jj, const uint8_t *frame_owned,
                                  int HW, int t0, int P, int update_poses, int update_disps, float *dz_out,
-                                 float *dx_out, BaTables T, BaBuffers W, float disp_floor);
+                                 float *dx_out, BaTables T, BaBuffers W, float disp_floor, const int *skip);
 __global__ void ba_copy_f32_kernel(const float *src, float *dst, int n);
+// dba_bacore_retract_device (ba_host.hip) on a planned workspace: what inertial.hip ends its step with
+int ba_retract_device(const BaPlan &plan, float *poses, float *disps, const int64_t *jj, const double *dx_dev, const int *skip_dev,
+                      float *dx_out, float *dz_out, hipStream_t stream);
 __global__ void ba_gather_edges_kernel(const float2 *tgt_inac, const float2 *wgt_inac, const int64_t *ii_inac, const int64_t *jj_inac,
                                        const int64_t *sel, int n_sel, int n_inac, const float2 *tgt_act, const float2 *wgt_act,
                                        const int64_t *ii_act, const int64_t *jj_act, int HW, float *tgt_out, float *wgt_out,

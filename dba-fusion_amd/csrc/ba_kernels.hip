@@ -1901,8 +1901,9 @@ __global__ __launch_bounds__(256) void ba_update_kernel(float *__restrict__ pose
                                                         int t0, int P, int update_poses, int update_disps,
                                                         float *__restrict__ dz_out,
                                                         float *__restrict__ dx_out, BaTables T, BaBuffers W,
-                                                        float disp_floor) {
+                                                        float disp_floor, const int *__restrict__ skip) {
   const int m = blockIdx.y;
+  if (skip && skip[0]) return;   // (dba_bacore_retract_device: the caller's solve on the device failed, nothing moves)
   if (T.gkey[7]) {   // stage 0 refused the call (eta rows != |kx|): the state stays as it is, the caller gets zero updates
     if (m == T.Mmax && blockIdx.x == 0 && dx_out)
       for (int i = threadIdx.x; i < 6 * P; i += blockDim.x) dx_out[i] = 0.f;

@@ -115,10 +115,13 @@ __global__ __launch_bounds__(DV_THREADS) void dv_factor_kernel(const double *__r
   if (tid == 0) status[0] = *bad;
 }
 
-// Column c of M into y[0, n), by ONE wave: L y = e_c forwards (from row c on), L^T x = y backwards; the 64 lanes share each
-// row's dot product (lane t & 63 owns y[t]: no lane reads what another wrote) and add their parts in a xor butterfly, which
-// leaves the same bits in every lane.  y: n doubles of LDS that belong to this wave.  No workgroup barrier.
-__device__ __forceinline__ void dv_solve_column(const double *__restrict__ Lg, int n, int c, double *y, int lane) {
+// Sd^-1 rhs into y[0, n), by ONE wave: L y = rhs forwards (from row c on: the entries of rhs before row c are zero, rhs(i) is
+// asked for i >= c only), L^T x = y backwards; the 64 lanes share each row's dot product (lane t & 63 owns y[t]: no lane reads
+// what another wrote) and add their parts in a xor butterfly, which leaves the same bits in every lane.  y: n doubles of LDS
+// that belong to this wave.  No workgroup barrier.  dv_solve_column: rhs = e_c, column c of M (the stages of this header);
+// inertial.hip solves its one right-hand side with c = 0.
+template <class Rhs>
+__device__ __forceinline__ void dv_solve_rhs(const double *__restrict__ Lg, int n, int c, Rhs rhs, double *y, int lane) {
   for (int t = lane; t < n; t += 64) y[t] = 0.0;
   const int tb = c & ~63;
   for (int i = c; i < n; i++) {
@@ -126,7 +129,7 @@ __device__ __forceinline__ void dv_solve_column(const double *__restrict__ Lg, i
     double s = 0.0;
     for (int t = tb + lane; t < i; t += 64) s = fma(row[t], y[t], s);
     s = dv_wave_sum(s);
-    if ((i & 63) == lane) y[i] = ((i == c ? 1.0 : 0.0) - s) / row[i];
+    if ((i & 63) == lane) y[i] = (rhs(i) - s) / row[i];
   }
   for (int i = n - 1; i >= 0; i--) {
     const double *row = Lg + (size_t)i * n;        // above the diagonal: L^T
@@ -135,6 +138,9 @@ __device__ __forceinline__ void dv_solve_column(const double *__restrict__ Lg, i
     s = dv_wave_sum(s);
     if ((i & 63) == lane) y[i] = (y[i] - s) / row[i];
   }
+}
+__device__ __forceinline__ void dv_solve_column(const double *__restrict__ Lg, int n, int c, double *y, int lane) {
+  dv_solve_rhs(Lg, n, c, [c](int i) { return i == c ? 1.0 : 0.0; }, y, lane);
 }
 
 // launch 1 of both stages: the factor of the n x n system in the workspace's H into the scratch

@@ -67,6 +67,12 @@ class FrameItem(ctypes.Structure):
                [("pose", c_float * 7), ("intr", c_float * 4), ("disp_fill", c_float)]
 
 
+class InertialState(ctypes.Structure):
+    """dba_inertial_state of include/dba_hip.h"""
+    _fields_ = [(n, c_void_p) for n in ("R", "p", "vel", "bias", "prior_R", "prior_p", "prior_vel", "prior_bias", "prior_w")] + \
+               [("gravity", ctypes.c_double * 3)]
+
+
 # every exported symbol of include/dba_hip.h with its (restype, argtypes); pointers are void*
 _P = c_void_p
 SYMBOLS = {
@@ -126,6 +132,11 @@ SYMBOLS = {
     "dba_ba_depth_variance_parts": (c_int, [c_int] * 6 + [c_float, c_float, _P, c_int, _P, c_size_t, _P, c_size_t, _P, c_int]),
     "dba_ba_pose_covariance": (c_int, [_P] + [c_int] * 6 + [c_float, c_float, _P, c_int, _P, c_int, _P, _P, c_int, _P, c_int,
                                        _P, c_size_t, _P, c_size_t, _P]),
+    "dba_bacore_retract_device": (c_int, [_P] * 4 + [c_int] * 6 + [_P, _P, _P, _P, _P, c_size_t, _P]),
+    "dba_inertial_scratch_bytes": (c_size_t, [c_int]),
+    "dba_inertial_linearize": (c_int, [ctypes.POINTER(InertialState), c_int, _P, c_int, _P, _P, _P, _P, c_size_t, _P]),
+    "dba_inertial_step": (c_int, [ctypes.POINTER(InertialState), c_int, _P, c_int, _P, ctypes.c_double, c_float, c_float,
+                                  _P, _P, _P, _P] + [c_int] * 6 + [_P, _P, _P, c_size_t, _P, c_size_t, _P]),
     "dba_ba_cost_scratch_bytes": (c_size_t, [c_int] * 3),
     "dba_ba_cost": (c_int, [_P] * 7 + [c_int] * 4 + [_P, c_int, _P, c_size_t, _P]),
     "dba_corr_index_forward": (c_int, [_P, _P, _P] + [c_int] * 7 + [_P]),

@@ -422,6 +422,64 @@ int dba_ba_pose_covariance(const float *poses, int N, int B, int ht, int wd, int
                            double *out_pairs, int out_pair_rows, void *scratch, size_t scratch_bytes, void *ws, size_t ws_bytes,
                            dba_stream_t stream);
 
+/* dba_bacore_retract with the increment in DEVICE memory: dx_dev [6 (t1 - t0)] float64, BA tangents, is rounded to float32 into
+ * the workspace's update slot and applied by the same back-substitution + retraction launch.  skip_dev (device, may be NULL):
+ * when the word it points to is not zero as the launches run, neither poses nor inverse depths move and dx_out, dz_out are not
+ * written.  No host synchronisation; two launches.  DBA_ERR_ARG for a null dx_dev, poses, disps or jj and for sizes ba_plan
+ * refuses, DBA_ERR_WORKSPACE for a workspace that is too small: before any runtime call. */
+int dba_bacore_retract_device(float *poses, float *disps, const int64_t *ii, const int64_t *jj, int N, int B, int ht, int wd, int t0,
+                              int t1, const double *dx_dev, const int *skip_dev, float *dx_out, float *dz_out, void *ws,
+                              size_t ws_bytes, dba_stream_t stream);
+
+/* Inertial factors in the window solve (csrc/inertial.hip; dbaf_amd/inertial.py is the public interface and states the
+ * residual).  P inertial states, world <- body, all float64 on the device: R [P, 3, 3] row-major, p [P, 3], vel [P, 3],
+ * bias [P, 6] = (ba, bg).  The tangent of a state is (dphi, dp, dv, dba, dbg): R <- R Exp(dphi), p <- p + R dp, vel += dv,
+ * bias += db; (dphi, dp) are the coordinates dba_bacore_hessian_host's layout 1 delivers the visual system in.
+ * Optional diagonal priors: anchors prior_R, prior_p, prior_vel, prior_bias (shaped like the state) and prior_w [P, 15] =
+ * mask / sigma^2 per tangent entry; all five NULL: no prior.  The residual of a prior is the tangent at the anchor that
+ * leads to the state.
+ * preint [preint_rows >= P - 1, DBA_INERTIAL_K]: one row per interval k -> k + 1,
+ *     dR 9 | dv 3 | dp 3 | dt 1 | dR/dbg 9 | dv/dba 9 | dv/dbg 9 | dp/dba 9 | dp/dbg 9 | linearisation bias 6 | L9 81 | L6 36
+ * (matrices row-major; L9 the INVERSE of the 9 x 9 covariance in the order phi, v, p; L6 the inverse of the bias random walk's).
+ * The struct is read on the host (pointers and gravity travel as kernel arguments); what it points to is device memory. */
+#define DBA_INERTIAL_K 184
+#define DBA_INERTIAL_MAX_P 25 /* 15 P <= 384: the one-workgroup float64 Cholesky of csrc/reduced_inverse.h */
+typedef struct {
+  double *R, *p, *vel, *bias;
+  const double *prior_R, *prior_p, *prior_vel, *prior_bias, *prior_w;
+  double gravity[3];
+} dba_inertial_state;
+
+/* bytes of the scratch both entries below work in for P states; 0 for a P they refuse */
+size_t dba_inertial_scratch_bytes(int P);
+
+/* Launch (a) alone: per interval r [15], J^T L J [30, 30] and J^T L r [30] over the tangents of its two states, and per state
+ * the prior's terms (into the scratch).  r_out [>= P - 1, 15], H_out [>= P - 1, 30, 30], g_out [>= P - 1, 30]: float64,
+ * device, each may be NULL (the scratch's own slots are always written).  One launch, one workgroup per state, no atomics.
+ * Refused BEFORE ANY RUNTIME CALL: DBA_ERR_ARG for a null st, R, p, vel, bias, preint or scratch, priors given in part,
+ * a misaligned pointer, P < 2 or preint_rows < P - 1; DBA_ERR_UNSUPPORTED for P > DBA_INERTIAL_MAX_P; DBA_ERR_WORKSPACE for
+ * scratch_bytes < dba_inertial_scratch_bytes(P). */
+int dba_inertial_linearize(const dba_inertial_state *st, int P, const double *preint, int preint_rows, double *r_out,
+                           double *H_out, double *g_out, void *scratch, size_t scratch_bytes, dba_stream_t stream);
+
+/* One visual-inertial Gauss-Newton step on the device, after a linearisation + reduction (dba_bacore_hessian_host) on `ws`:
+ *   (a) dba_inertial_linearize;
+ *   (b) the 15 P x 15 P system M dx = rhs in one fixed order, every entry owned by one lane, no atomics: the window's H, v read
+ *       from the workspace, with `stabilizer` on the first six diagonal entries and the congruence by A36 (6 x 6 row-major,
+ *       HOST: the block of dba_bacore_hessian_host's layout 1, dx_ba = A dx_g) exactly as that entry's export applies them,
+ *       in the pose slots; then the interval before the state, the interval after it, the prior.  rhs = vg - sum J^T L r;
+ *   (c) Md = M + diag(ep + lm diag(M)) = L L^T and the two substitutions, by the kernels of csrc/reduced_inverse.h;
+ *   (d) the retraction of the inertial states, dx_ba = A dx_g for the pose part, and dba_bacore_retract_device.
+ * dx_out [P, 15] float64, device.  status_out (device int, may be NULL): 1 when a pivot was not positive -- then dx_out is NaN
+ * and neither the inertial states nor poses nor inverse depths move -- else 0.  Six launches, all float64, bit-identical from
+ * run to run, no host synchronisation (records into a hipGraph).  poses, disps, ii, jj, N .. t1, ws as for dba_bacore_retract.
+ * Refused BEFORE ANY RUNTIME CALL: what dba_inertial_linearize refuses, a null A36, dx_out, poses, disps or jj, sizes ba_plan
+ * refuses or a window that is not P poses wide (DBA_ERR_ARG), a workspace that is too small (DBA_ERR_WORKSPACE). */
+int dba_inertial_step(const dba_inertial_state *st, int P, const double *preint, int preint_rows, const double *A36,
+                      double stabilizer, float lm, float ep, float *poses, float *disps, const int64_t *ii, const int64_t *jj, int N,
+                      int B, int ht, int wd, int t0, int t1, double *dx_out, int *status_out, void *scratch, size_t scratch_bytes,
+                      void *ws, size_t ws_bytes, dba_stream_t stream);
+
 /* The BA cost report (csrc/ba_cost.hip): what the linearisation minimises, per edge.  For edge n with i = ii[n], j = jj[n] and
  * pixel k = v * wd + u: Gij = Tj Ti^-1 (i == j: the fixed stereo baseline t = (-0.1, 0, 0), q = identity) formed in float64
  * and rounded once, X = ((u - cx) / fx, (v - cy) / fy, 1), d = disps[i, k], (x, y, z) = R X + d t.  A pixel with z < 0.25 is
