@@ -68,6 +68,63 @@ def _identity_slots(n, device):
     return t
 
 
+def _rows(shape, cols):
+    """rows of a tensor that is used as [-1, cols], or None where its last extent is not `cols`"""
+    if len(shape) == 0 or shape[-1] != cols:
+        return None
+    rows = 1
+    for s in shape[:-1]:
+        rows *= s
+    return rows
+
+
+def _check_reproject_shapes(n_slots, h1, w1, poses_shape, disps_shape, K_shape, ii_shape, jj_shape, ii_dtype, jj_dtype):
+    """The extents the fused lookups' kernels rely on, from shapes and dtypes alone (no tensor is touched, nothing is read
+    from the device): they read poses[ix], K[ix] and disps[ix] for every frame index ix of ii and jj, and ii[e], jj[e] for
+    every edge e of the block (n_slots edges, h1 x w1 maps).  Raises ValueError naming the operand.  The index VALUES stay
+    the caller's contract, as for the geometry entries: checking them would need a device read.
+    (Runs once per lookup on the host: a message is only put together for the check that fails.)"""
+    op = "lookup_reprojected"
+
+    def fail(msg):
+        _lib.require(False, op, msg)
+
+    if len(disps_shape) < 2:
+        fail("disps must be [B, h, w] or [1, B, h, w], got %s" % (tuple(disps_shape),))
+    if disps_shape[-2] != h1 or disps_shape[-1] != w1:
+        fail("disps has %d x %d maps, the block was built for %d x %d" % (disps_shape[-2], disps_shape[-1], h1, w1))
+    B = 1
+    for s in disps_shape[:-2]:
+        B *= s
+    if B < 1:
+        fail("disps holds no frame")
+    p_rows = _rows(poses_shape, 7)
+    if p_rows is None:
+        fail("poses must be [B, 7] or [1, B, 7], got %s" % (tuple(poses_shape),))
+    if p_rows < B:
+        fail("poses has %d rows, fewer than the %d frames of disps" % (p_rows, B))
+    k_rows = _rows(K_shape, 4)
+    if k_rows is None:
+        fail("intrinsics must be [4], [B, 4] or [1, B, 4], got %s" % (tuple(K_shape),))
+    if k_rows != 1 and k_rows != B:
+        fail("intrinsics must have 1 row or one per frame of disps (%d), got %d" % (B, k_rows))
+    if len(ii_shape) != 1:
+        fail("ii must be 1-D, got %s" % (tuple(ii_shape),))
+    if len(jj_shape) != 1:
+        fail("jj must be 1-D, got %s" % (tuple(jj_shape),))
+    if ii_dtype not in _INDEX_DTYPES:
+        fail("ii must be of an integer dtype, got %s" % (ii_dtype,))
+    if jj_dtype not in _INDEX_DTYPES:
+        fail("jj must be of an integer dtype, got %s" % (jj_dtype,))
+    if ii_shape[0] != jj_shape[0]:
+        fail("ii and jj must have the same length, got %d and %d" % (ii_shape[0], jj_shape[0]))
+    if ii_shape[0] != n_slots:
+        fail("ii and jj have %d edges, the block holds %d" % (ii_shape[0], n_slots))
+
+
+_INDEX_DTYPES = (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8)
+
+
 class CorrBlock:
     """layout="sheared" (default when the shapes allow it) keeps every level flow-aligned,
     Vs_l[slot, dy, dx, pixel] with pixel = y1 * w1 + x1 and the pixel axis padded to a multiple of 64
@@ -393,7 +450,8 @@ class CorrBlock:
         CorrBlock.__call__ in ONE launch: the lookup kernel computes its pixels' coordinates in its prologue.
         poses [B,7] (or [1,B,7] / an SE3), disps [B,h,w] (or [1,B,h,w]), intrinsics [B,4] / [1,B,4] / [4]; ii, jj [n].
         Returns (corr [1,n,L*49,h,w], coords [1,n,h,w,2], valid [1,n,h,w,1]) -- corr and coords bit-identical to
-        projective_transform followed by __call__."""
+        projective_transform followed by __call__.  Extents that do not fit each other or the block raise ValueError before
+        anything is built or launched (_check_reproject_shapes); the index values are the caller's contract."""
         return self._lookup_reprojected(poses, disps, intrinsics, ii, jj, None, timing)
 
     def lookup_motion(self, poses, disps, intrinsics, ii, jj, target, timing=None):
@@ -415,8 +473,11 @@ class CorrBlock:
     def _lookup_reprojected(self, poses, disps, intrinsics, ii, jj, target, timing):
         if self.layout != "sheared":
             raise RuntimeError("lookup_reprojected needs the flow-aligned layout")
-        self._materialise()
         pdata = poses.data if hasattr(poses, "data") and not isinstance(poses, torch.Tensor) else poses
+        # the kernels index poses, disps, K, ii and jj unchecked: refuse what they would read past, before anything is built
+        _check_reproject_shapes(self.n, self.h1, self.w1, pdata.shape, disps.shape, intrinsics.shape, ii.shape, jj.shape,
+                                ii.dtype, jj.dtype)
+        self._materialise()
         pdata = pdata.reshape(-1, 7).float().contiguous()
         d = disps.reshape(-1, disps.shape[-2], disps.shape[-1]).float().contiguous()
         B, ht, wd = d.shape
@@ -424,8 +485,7 @@ class CorrBlock:
         K = (K.expand(B, 4) if K.shape[0] == 1 else K).contiguous()
         ii = ii.to(device=d.device, dtype=torch.int64).contiguous()
         jj = jj.to(device=d.device, dtype=torch.int64).contiguous()
-        n = int(ii.shape[0])
-        assert n == self.n and (ht, wd) == (self.h1, self.w1), "edge count / map size mismatch"
+        n = int(ii.shape[0])      # (== self.n, and (ht, wd) == (self.h1, self.w1): _check_reproject_shapes)
         coords = torch.empty(1, n, ht, wd, 2, dtype=torch.float32, device=d.device)
         valid = torch.empty(1, n, ht, wd, 1, dtype=torch.float32, device=d.device)
         rd = 2 * self.radius + 1
