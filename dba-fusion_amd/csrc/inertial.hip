@@ -17,6 +17,21 @@
 // The scratch, in doubles (in_layout): Hf [P-1][900] | gf [P-1][30] | rf [P-1][15] | Hp [P][225] | gp [P][15] | M [n][n] |
 // rhs [n] | dx_ba [6P] | then the scratch of reduced_inverse.h for n = 15 P (L, its unused M, the status word).
 // All arithmetic is float64; there are no atomics; no kernel indexes beyond what P states.
+//
+// The dense prior (dba_inertial_state.dense_*): H [15K][15K], b [15K] at a linearisation point x0 of the first K states.
+// (a) forms delta_k = local(x0_k, x_k) by lane 0 of state k < K; (b) adds H to M and b - H delta to rhs, the row of H delta
+// summed with t ascending by the owner lane of the entry.  No dense prior: the term is skipped.  delta lives in the first
+// 15 P doubles of the reduced_inverse scratch's unused M.
+//
+// Marginalisation (dba_inertial_marginalize): the Schur complement over the m oldest states, four launches behind (a):
+//   (e) in_marg_assemble_kernel   the system over S states, the terms of (b) restricted to what touches the departing states
+//                             (in_entry: one text for both assemblies), written as M_mm [15m][15m] | M_km | M_kk and rhs [15S]
+//   (f) dv_factor_kernel      M_mm = L L^T, no damping
+//   (g) in_marg_forward_kernel    W = L^-1 [M_mk | rhs_m]: one wave and one workgroup per column, dv_forward_rhs
+//   (h) in_marg_schur_kernel  H_new = M_kk - W W^T (lower triangle, mirrored), b_new = rhs_k - W w, the linearisation point;
+//                             a status word that is set makes H_new and b_new NaN and writes nothing else.
+// The three parts of the marginal system share the scratch's M (15m x 15m + 15(S-m) x 15m + (15(S-m))^2 <= (15S)^2), W follows
+// delta in the reduced_inverse scratch's unused M.
 #include "reduced_inverse.h"
 
 namespace dba {
@@ -35,7 +50,10 @@ static_assert(PK_L6 + 36 == IN_K, "the packed row");
 struct InLayout {   // the parts of a scratch of in_scratch_bytes(P) bytes
   double *Hf, *gf, *rf, *Hp, *gp, *M, *rhs, *dxba;
   void *dv;
-  InLayout(void *scratch, int P) {
+  double *delta() const { return static_cast<double *>(dv) + (size_t)225 * P * P; }   // [15 P], in the unused M of dv
+  double *W() const { return delta() + (size_t)15 * P; }                             // the marginalisation's [15 (S - m) + 1][15 m]
+  int P;
+  InLayout(void *scratch, int P_) : P(P_) {
     const size_t n = (size_t)15 * P;
     Hf = static_cast<double *>(scratch);
     gf = Hf + (size_t)900 * (P - 1);
@@ -57,6 +75,8 @@ struct InState {   // dba_inertial_state as the kernels take it
   double *R, *p, *vel, *bias;
   const double *pR, *pp, *pv, *pb, *pw;
   double g[3];
+  const double *dR, *dp, *dvel, *dbias, *dH, *db;   // the dense prior over the first dK states; dH null: none
+  int dK;
 };
 
 // ---- 3 x 3, row-major -------------------------------------------------------------------------------------------------------
@@ -199,13 +219,25 @@ __device__ void in_prior(const InState &st, int k, double *r, double *J) {
   for (int i = 6; i < 15; i++) J[i * 15 + i] = 1.0;
 }
 
+// d [15] = local(x0_k, x_k) of the dense prior: (Log(R0^T R), R0^T (p - p0), v - v0, bias - bias0), by one lane
+__device__ void in_local(const InState &st, int k, double *d) {
+  double Rr[9], x[3];
+  m3_tmul(st.dR + 9 * k, st.R + 9 * k, Rr);
+  so3_log(Rr, d);
+  for (int i = 0; i < 3; i++) x[i] = st.p[3 * k + i] - st.dp[3 * k + i];
+  m3_tvec(st.dR + 9 * k, x, d + 3);
+  for (int i = 0; i < 3; i++) d[6 + i] = st.vel[3 * k + i] - st.dvel[3 * k + i];
+  for (int i = 0; i < 6; i++) d[9 + i] = st.bias[6 * k + i] - st.dbias[6 * k + i];
+}
+
 __global__ __launch_bounds__(IN_THREADS) void in_linearize_kernel(InState st, int P, const double *__restrict__ preint,
                                                                   double *__restrict__ r_out, double *__restrict__ H_out,
                                                                   double *__restrict__ g_out, double *__restrict__ Hp,
-                                                                  double *__restrict__ gp) {
+                                                                  double *__restrict__ gp, double *__restrict__ delta) {
   __shared__ double pk[IN_K], J[450], LJ[450], r[15], Lr[15];
   const int k = blockIdx.x, tid = threadIdx.x;
   if (k >= P) return;
+  if (st.dH && k < st.dK && tid == 0) in_local(st, k, delta + 15 * k);   // (read by the assembly launch alone)
   if (k < P - 1) {   // (uniform over the workgroup: every barrier below is reached by all of it)
     for (int e = tid; e < IN_K; e += IN_THREADS) pk[e] = preint[(size_t)IN_K * k + e];
     for (int e = tid; e < 450; e += IN_THREADS) J[e] = 0.0;
@@ -268,34 +300,27 @@ __global__ __launch_bounds__(IN_THREADS) void in_linearize_kernel(InState st, in
   }
 }
 
-// H6, b6: the BA workspace's reduced camera system (6P unknowns, LOWER triangle); M [n][n] full, rhs [n], n = 15 P
-__global__ __launch_bounds__(IN_THREADS) void in_assemble_kernel(const double *__restrict__ H6, const double *__restrict__ b6, int P,
-                                                                 ExportArg arg, double stab, const double *__restrict__ Hf,
-                                                                 const double *__restrict__ gf, const double *__restrict__ Hp,
-                                                                 const double *__restrict__ gp, double *__restrict__ M,
-                                                                 double *__restrict__ rhs) {
-  const int n = 15 * P, n6 = 6 * P;
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= n * n + n) return;
-  if (idx >= n * n) {
-    const int i = idx - n * n, s = i / 15, a = i - 15 * s;
-    double v = 0.0;
-    if (a < 6) {   // vg = sum_k A[k][a] v[6 s + k]
-#pragma unroll
-      for (int k = 0; k < 6; k++) v = fma(arg.A[6 * k + a], b6[6 * s + k], v);
-    }
-    if (s >= 1) v -= gf[(size_t)30 * (s - 1) + 15 + a];
-    if (s < P - 1) v -= gf[(size_t)30 * s + a];
-    v -= gp[(size_t)15 * s + a];
-    rhs[i] = v;
-    return;
-  }
-  const int i = idx / n, j = idx - i * n, hi = max(i, j), lo = min(i, j);
-  const int si = hi / 15, a = hi - 15 * si, sj = lo / 15, c = lo - 15 * sj;
+// The terms an entry of a system over the states' tangents takes, in the order they are added: the visual system (H6, b6: a BA
+// workspace's reduced camera system over Pv poses, LOWER triangle; states < Pv), the intervals k < nI (before the state, then
+// after it), the diagonal priors of the states < nP, the dense prior over the first nd unknowns (dH null: skipped).
+struct InTerms {
+  const double *H6, *b6;
+  int Pv;
+  const double *Hf, *gf;
+  int nI;
+  const double *Hp, *gp;
+  int nP;
+  const double *dH, *db, *delta;
+  int nd;
+};
+
+// entry (hi, lo), hi >= lo, of the system's matrix
+__device__ inline double in_entry(const InTerms &T, const ExportArg &arg, double stab, int hi, int lo) {
+  const int si = hi / 15, a = hi - 15 * si, sj = lo / 15, c = lo - 15 * sj, n6 = 6 * T.Pv;
   double v = 0.0;
-  if (a < 6 && c < 6) {   // (A^T (H + stabiliser) A)[6 si + a][6 sj + c], as ba_export_kernel forms it
+  if (a < 6 && c < 6 && si < T.Pv) {   // (A^T (H + stabiliser) A)[6 si + a][6 sj + c], as ba_export_kernel forms it
     auto h = [&](int r, int q) {
-      const double x = H6[(size_t)max(r, q) * n6 + min(r, q)];
+      const double x = T.H6[(size_t)max(r, q) * n6 + min(r, q)];
       return (r == q && r < 6) ? x + stab : x;
     };
 #pragma unroll
@@ -306,11 +331,120 @@ __global__ __launch_bounds__(IN_THREADS) void in_assemble_kernel(const double *_
       v = fma(arg.A[6 * k + a], t, v);
     }
   }
-  if (si >= 1 && sj == si) v += Hf[(size_t)900 * (si - 1) + 30 * (15 + a) + 15 + c];
-  if (si >= 1 && sj == si - 1) v += Hf[(size_t)900 * (si - 1) + 30 * (15 + a) + c];
-  if (si < P - 1 && sj == si) v += Hf[(size_t)900 * si + 30 * a + c];
-  if (sj == si) v += Hp[(size_t)225 * si + 15 * a + c];
-  M[idx] = v;
+  if (si >= 1 && si - 1 < T.nI && sj == si) v += T.Hf[(size_t)900 * (si - 1) + 30 * (15 + a) + 15 + c];
+  if (si >= 1 && si - 1 < T.nI && sj == si - 1) v += T.Hf[(size_t)900 * (si - 1) + 30 * (15 + a) + c];
+  if (si < T.nI && sj == si) v += T.Hf[(size_t)900 * si + 30 * a + c];
+  if (si < T.nP && sj == si) v += T.Hp[(size_t)225 * si + 15 * a + c];
+  if (T.dH && hi < T.nd) v += T.dH[(size_t)hi * T.nd + lo];
+  return v;
+}
+
+// entry i of the system's right-hand side
+__device__ inline double in_rhs_entry(const InTerms &T, const ExportArg &arg, int i) {
+  const int s = i / 15, a = i - 15 * s;
+  double v = 0.0;
+  if (a < 6 && s < T.Pv) {   // vg = sum_k A[k][a] v[6 s + k]
+#pragma unroll
+    for (int k = 0; k < 6; k++) v = fma(arg.A[6 * k + a], T.b6[6 * s + k], v);
+  }
+  if (s >= 1 && s - 1 < T.nI) v -= T.gf[(size_t)30 * (s - 1) + 15 + a];
+  if (s < T.nI) v -= T.gf[(size_t)30 * s + a];
+  if (s < T.nP) v -= T.gp[(size_t)15 * s + a];
+  if (T.dH && i < T.nd) {    // b - H delta, the row's sum with t ascending
+    const double *row = T.dH + (size_t)i * T.nd;
+    double hd = 0.0;
+    for (int t = 0; t < T.nd; t++) hd = fma(row[t], T.delta[t], hd);
+    v += T.db[i] - hd;
+  }
+  return v;
+}
+
+// M [n][n] full, rhs [n], n = 15 P: the step's system (T.Pv = T.nP = P, T.nI = P - 1)
+__global__ __launch_bounds__(IN_THREADS) void in_assemble_kernel(InTerms T, int P, ExportArg arg, double stab, double *__restrict__ M,
+                                                                 double *__restrict__ rhs) {
+  const int n = 15 * P;
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= n * n + n) return;
+  if (idx >= n * n) {
+    rhs[idx - n * n] = in_rhs_entry(T, arg, idx - n * n);
+    return;
+  }
+  const int i = idx / n, j = idx - i * n;
+  M[idx] = in_entry(T, arg, stab, max(i, j), min(i, j));
+}
+
+// The marginal system over S states, nm = 15 m departing unknowns first: Mmm [nm][nm] (the row length dv_factor_kernel takes),
+// Mkm [nk][nm], Mkk [nk][nk], nk = 15 (S - m), and rhs [15 S].  One owner lane per entry; M_mk is M_km transposed and is not stored.
+__global__ __launch_bounds__(IN_THREADS) void in_marg_assemble_kernel(InTerms T, int S, int m, ExportArg arg, double stab,
+                                                                      double *__restrict__ Mmm, double *__restrict__ Mkm,
+                                                                      double *__restrict__ Mkk, double *__restrict__ rhs) {
+  const int n = 15 * S, nm = 15 * m, nk = n - nm;
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= n * n + n) return;
+  if (idx >= n * n) {
+    rhs[idx - n * n] = in_rhs_entry(T, arg, idx - n * n);
+    return;
+  }
+  const int i = idx / n, j = idx - i * n;
+  if (i < nm && j >= nm) return;
+  const double v = in_entry(T, arg, stab, max(i, j), min(i, j));
+  if (i < nm) Mmm[(size_t)i * nm + j] = v;
+  else if (j < nm) Mkm[(size_t)(i - nm) * nm + j] = v;
+  else Mkk[(size_t)(i - nm) * nk + j - nm] = v;
+}
+
+// W [nk + 1][nm]: row c < nk = L^-1 (column c of M_mk = row c of Mkm), row nk = L^-1 rhs_m.  One wave per workgroup and column.
+__global__ __launch_bounds__(64) void in_marg_forward_kernel(const double *__restrict__ Lg, const int *__restrict__ status, int nm,
+                                                             int nk, const double *__restrict__ Mkm, const double *__restrict__ rhs,
+                                                             double *__restrict__ W) {
+  __shared__ double y[15 * (IN_MAX_P - 1)];
+  const int c = blockIdx.x, lane = threadIdx.x;
+  if (c > nk || status[0]) return;   // (no factor: the Schur launch writes NaN and reads nothing of W)
+  const double *src = c < nk ? Mkm + (size_t)c * nm : rhs;
+  dv_forward_rhs(Lg, nm, 0, [src](int i) { return src[i]; }, y, lane);
+  for (int t = lane; t < nm; t += 64) W[(size_t)c * nm + t] = y[t];   // (lane t & 63 owns y[t])
+}
+
+// H_new [nk][nk] = Mkk - W W^T: one lane per entry of the lower triangle, the sum with t ascending, mirrored; b_new [nk]; the
+// linearisation point = the states m .. S - 1 (21 doubles each).  status set: H_new, b_new NaN, nothing else written.
+__global__ __launch_bounds__(IN_THREADS) void in_marg_schur_kernel(const int *__restrict__ status, int nm, int nk, int m,
+                                                                   const double *__restrict__ Mkk, const double *__restrict__ rhs,
+                                                                   const double *__restrict__ W, InState st, double *__restrict__ H_new,
+                                                                   double *__restrict__ b_new, double *__restrict__ R0,
+                                                                   double *__restrict__ p0, double *__restrict__ vel0,
+                                                                   double *__restrict__ bias0, int *__restrict__ status_out) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x, K = nk / 15;
+  const bool bad = status[0] != 0;
+  if (idx == 0 && status_out) status_out[0] = bad ? 1 : 0;
+  if (idx < nk * nk) {
+    const int i = idx / nk, j = idx - i * nk;
+    if (j > i) return;
+    double v = __builtin_nan("");
+    if (!bad) {
+      const double *wi = W + (size_t)i * nm, *wj = W + (size_t)j * nm;
+      double s = 0.0;
+      for (int t = 0; t < nm; t++) s = fma(wi[t], wj[t], s);
+      v = Mkk[idx] - s;
+    }
+    H_new[(size_t)i * nk + j] = v;
+    H_new[(size_t)j * nk + i] = v;
+  } else if (idx < nk * nk + nk) {
+    const int i = idx - nk * nk;
+    double v = __builtin_nan("");
+    if (!bad) {
+      const double *wi = W + (size_t)i * nm, *wr = W + (size_t)nk * nm;
+      double s = 0.0;
+      for (int t = 0; t < nm; t++) s = fma(wi[t], wr[t], s);
+      v = rhs[nm + i] - s;
+    }
+    b_new[i] = v;
+  } else if (idx < nk * nk + nk + 21 * K && !bad) {
+    const int e = idx - nk * nk - nk;
+    if (e < 9 * K) R0[e] = st.R[9 * m + e];
+    else if (e < 12 * K) p0[e - 9 * K] = st.p[3 * m + e - 9 * K];
+    else if (e < 15 * K) vel0[e - 12 * K] = st.vel[3 * m + e - 12 * K];
+    else bias0[e - 15 * K] = st.bias[6 * m + e - 15 * K];
+  }
 }
 
 __global__ __launch_bounds__(IN_THREADS) void in_solve_retract_kernel(const double *__restrict__ Lg, const int *__restrict__ status,
@@ -357,23 +491,29 @@ int in_check(const dba_inertial_state *st, int P, const double *preint, int prei
   const int given = (st->prior_R != nullptr) + (st->prior_p != nullptr) + (st->prior_vel != nullptr) + (st->prior_bias != nullptr) +
                     (st->prior_w != nullptr);
   if (given != 0 && given != 5) return DBA_ERR_ARG;
+  const int dense = (st->dense_R != nullptr) + (st->dense_p != nullptr) + (st->dense_vel != nullptr) + (st->dense_bias != nullptr) +
+                    (st->dense_H != nullptr) + (st->dense_b != nullptr);
+  if ((dense != 0 && dense != 6) || (dense == 0 && st->dense_K != 0)) return DBA_ERR_ARG;
   const void *ptrs[] = {st->R, st->p, st->vel, st->bias, st->prior_R, st->prior_p, st->prior_vel, st->prior_bias, st->prior_w,
-                        preint, scratch};
+                        st->dense_R, st->dense_p, st->dense_vel, st->dense_bias, st->dense_H, st->dense_b, preint, scratch};
   for (const void *q : ptrs)
     if (misaligned(q)) return DBA_ERR_ARG;
   if (P < 2 || preint_rows < P - 1) return DBA_ERR_ARG;
+  if (dense == 6 && (st->dense_K < 1 || st->dense_K > P)) return DBA_ERR_ARG;
   if (P > IN_MAX_P) return DBA_ERR_UNSUPPORTED;
   if (scratch_bytes < in_scratch_bytes(P)) return DBA_ERR_WORKSPACE;
   out->R = st->R, out->p = st->p, out->vel = st->vel, out->bias = st->bias;
   out->pR = st->prior_R, out->pp = st->prior_p, out->pv = st->prior_vel, out->pb = st->prior_bias, out->pw = st->prior_w;
   for (int i = 0; i < 3; i++) out->g[i] = st->gravity[i];
+  out->dR = st->dense_R, out->dp = st->dense_p, out->dvel = st->dense_vel, out->dbias = st->dense_bias;
+  out->dH = st->dense_H, out->db = st->dense_b, out->dK = st->dense_K;
   return DBA_OK;
 }
 
 int in_launch_linearize(const InState &s, int P, const double *preint, double *r_out, double *H_out, double *g_out,
                         const InLayout &lay, hipStream_t stream) {
   hipLaunchKernelGGL(in_linearize_kernel, dim3(P), dim3(IN_THREADS), 0, stream, s, P, preint, r_out ? r_out : lay.rf,
-                     H_out ? H_out : lay.Hf, g_out ? g_out : lay.gf, lay.Hp, lay.gp);
+                     H_out ? H_out : lay.Hf, g_out ? g_out : lay.gf, lay.Hp, lay.gp, lay.delta());
   DBA_LAUNCH_CHECK();
   return DBA_OK;
 }
@@ -386,6 +526,7 @@ using namespace dba;
 extern "C" {
 
 size_t dba_inertial_scratch_bytes(int P) { return (P < 2 || P > IN_MAX_P) ? 0 : in_scratch_bytes(P); }
+size_t dba_inertial_marg_scratch_bytes(int P) { return dba_inertial_scratch_bytes(P); }   // (one scratch serves both entries)
 
 int dba_inertial_linearize(const dba_inertial_state *st, int P, const double *preint, int preint_rows, double *r_out,
                            double *H_out, double *g_out, void *scratch, size_t scratch_bytes, dba_stream_t stream) {
@@ -413,14 +554,59 @@ int dba_inertial_step(const dba_inertial_state *st, int P, const double *preint,
   ExportArg arg;
   for (int e = 0; e < 36; e++) arg.A[e] = A36[e];
   if (const int rc = in_launch_linearize(s, P, preint, nullptr, nullptr, nullptr, lay, hs)) return rc;
-  hipLaunchKernelGGL(in_assemble_kernel, dim3((n * n + n + IN_THREADS - 1) / IN_THREADS), dim3(IN_THREADS), 0, hs, plan.W.H, plan.W.b,
-                     P, arg, stabilizer, lay.Hf, lay.gf, lay.Hp, lay.gp, lay.M, lay.rhs);
+  const InTerms terms = {plan.W.H, plan.W.b, P, lay.Hf, lay.gf, P - 1, lay.Hp, lay.gp, P, s.dH, s.db, lay.delta(), 15 * s.dK};
+  hipLaunchKernelGGL(in_assemble_kernel, dim3((n * n + n + IN_THREADS - 1) / IN_THREADS), dim3(IN_THREADS), 0, hs, terms, P, arg,
+                     stabilizer, lay.M, lay.rhs);
   DBA_LAUNCH_CHECK();
   if (const int rc = dv_launch_factor(lay.M, n, lm, ep, sc, hs)) return rc;
   hipLaunchKernelGGL(in_solve_retract_kernel, dim3(1), dim3(IN_THREADS), 0, hs, sc.Lg, sc.status, P, lay.rhs, s, arg, dx_out, lay.dxba,
                      status_out);
   DBA_LAUNCH_CHECK();
   return ba_retract_device(plan, poses, disps, jj, lay.dxba, sc.status, nullptr, nullptr, hs);
+}
+
+int dba_inertial_marginalize(const dba_inertial_state *st, int P, const double *preint, int preint_rows, const double *A36,
+                             double stabilizer, int m, int N, int B, int ht, int wd, int t0, int t1, void *ws, size_t ws_bytes,
+                             double *H_new, int h_rows, double *b_new, int b_rows, double *R0, double *p0, double *vel0,
+                             double *bias0, int x0_rows, int *status_out, void *scratch, size_t scratch_bytes, dba_stream_t stream) {
+  InState s;
+  if (const int rc = in_check(st, P, preint, preint_rows, scratch, scratch_bytes, &s)) return rc;
+  if (!A36 || !H_new || !b_new || !R0 || !p0 || !vel0 || !bias0) return DBA_ERR_ARG;
+  for (const void *q : {(const void *)H_new, (const void *)b_new, (const void *)R0, (const void *)p0, (const void *)vel0,
+                        (const void *)bias0})
+    if (misaligned(q)) return DBA_ERR_ARG;
+  if (m < 1 || m >= P) return DBA_ERR_ARG;
+  BaPlan plan;
+  int Pm = 0;
+  if (ws) {   // (no workspace: nothing visual was selected)
+    if (const int rc = ba_plan(N, B, ht, wd, t0, t1, ws, ws_bytes, &plan)) return rc;
+    Pm = plan.P;
+  }
+  if (Pm > P) return DBA_ERR_ARG;
+  const int S = std::max(std::max(Pm, m + 1), s.dH ? s.dK : 0), K = S - m;   // (dK <= P: in_check)
+  if (h_rows < 15 * K || b_rows < 15 * K || x0_rows < K) return DBA_ERR_ARG;
+
+  const InLayout lay(scratch, P);
+  const int n = 15 * S, nm = 15 * m, nk = 15 * K;
+  const DvScratch sc(lay.dv, 15 * P);   // (the factor of nm unknowns fills the head of L; the status word stays where the step's is)
+  hipStream_t hs = static_cast<hipStream_t>(stream);
+  ExportArg arg;
+  for (int e = 0; e < 36; e++) arg.A[e] = A36[e];
+  double *Mmm = lay.M, *Mkm = Mmm + (size_t)nm * nm, *Mkk = Mkm + (size_t)nk * nm;
+  if (const int rc = in_launch_linearize(s, P, preint, nullptr, nullptr, nullptr, lay, hs)) return rc;
+  const InTerms terms = {Pm ? plan.W.H : nullptr, Pm ? plan.W.b : nullptr, Pm, lay.Hf, lay.gf, m, lay.Hp, lay.gp, m, s.dH, s.db,
+                         lay.delta(), 15 * s.dK};
+  hipLaunchKernelGGL(in_marg_assemble_kernel, dim3((n * n + n + IN_THREADS - 1) / IN_THREADS), dim3(IN_THREADS), 0, hs, terms, S, m,
+                     arg, stabilizer, Mmm, Mkm, Mkk, lay.rhs);
+  DBA_LAUNCH_CHECK();
+  if (const int rc = dv_launch_factor(Mmm, nm, 0.0f, 0.0f, sc, hs)) return rc;
+  hipLaunchKernelGGL(in_marg_forward_kernel, dim3(nk + 1), dim3(64), 0, hs, sc.Lg, sc.status, nm, nk, Mkm, lay.rhs, lay.W());
+  DBA_LAUNCH_CHECK();
+  const int lanes = nk * nk + nk + 21 * K;
+  hipLaunchKernelGGL(in_marg_schur_kernel, dim3((lanes + IN_THREADS - 1) / IN_THREADS), dim3(IN_THREADS), 0, hs, sc.status, nm, nk, m,
+                     Mkk, lay.rhs, lay.W(), s, H_new, b_new, R0, p0, vel0, bias0, status_out);
+  DBA_LAUNCH_CHECK();
+  return DBA_OK;
 }
 
 }  // extern "C"

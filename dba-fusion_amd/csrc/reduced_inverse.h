@@ -120,8 +120,9 @@ __global__ __launch_bounds__(DV_THREADS) void dv_factor_kernel(const double *__r
 // what another wrote) and add their parts in a xor butterfly, which leaves the same bits in every lane.  y: n doubles of LDS
 // that belong to this wave.  No workgroup barrier.  dv_solve_column: rhs = e_c, column c of M (the stages of this header);
 // inertial.hip solves its one right-hand side with c = 0.
+// The forward half alone: L y = rhs from row c on.  inertial.hip runs it per column of its marginal system (c = 0).
 template <class Rhs>
-__device__ __forceinline__ void dv_solve_rhs(const double *__restrict__ Lg, int n, int c, Rhs rhs, double *y, int lane) {
+__device__ __forceinline__ void dv_forward_rhs(const double *__restrict__ Lg, int n, int c, Rhs rhs, double *y, int lane) {
   for (int t = lane; t < n; t += 64) y[t] = 0.0;
   const int tb = c & ~63;
   for (int i = c; i < n; i++) {
@@ -131,6 +132,10 @@ __device__ __forceinline__ void dv_solve_rhs(const double *__restrict__ Lg, int 
     s = dv_wave_sum(s);
     if ((i & 63) == lane) y[i] = (rhs(i) - s) / row[i];
   }
+}
+template <class Rhs>
+__device__ __forceinline__ void dv_solve_rhs(const double *__restrict__ Lg, int n, int c, Rhs rhs, double *y, int lane) {
+  dv_forward_rhs(Lg, n, c, rhs, y, lane);
   for (int i = n - 1; i >= 0; i--) {
     const double *row = Lg + (size_t)i * n;        // above the diagonal: L^T
     double s = 0.0;

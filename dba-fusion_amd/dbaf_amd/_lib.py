@@ -70,7 +70,8 @@ class FrameItem(ctypes.Structure):
 class InertialState(ctypes.Structure):
     """dba_inertial_state of include/dba_hip.h"""
     _fields_ = [(n, c_void_p) for n in ("R", "p", "vel", "bias", "prior_R", "prior_p", "prior_vel", "prior_bias", "prior_w")] + \
-               [("gravity", ctypes.c_double * 3)]
+               [("gravity", ctypes.c_double * 3)] + \
+               [(n, c_void_p) for n in ("dense_R", "dense_p", "dense_vel", "dense_bias", "dense_H", "dense_b")] + [("dense_K", c_int)]
 
 
 # every exported symbol of include/dba_hip.h with its (restype, argtypes); pointers are void*
@@ -137,6 +138,9 @@ SYMBOLS = {
     "dba_inertial_linearize": (c_int, [ctypes.POINTER(InertialState), c_int, _P, c_int, _P, _P, _P, _P, c_size_t, _P]),
     "dba_inertial_step": (c_int, [ctypes.POINTER(InertialState), c_int, _P, c_int, _P, ctypes.c_double, c_float, c_float,
                                   _P, _P, _P, _P] + [c_int] * 6 + [_P, _P, _P, c_size_t, _P, c_size_t, _P]),
+    "dba_inertial_marg_scratch_bytes": (c_size_t, [c_int]),
+    "dba_inertial_marginalize": (c_int, [ctypes.POINTER(InertialState), c_int, _P, c_int, _P, ctypes.c_double] + [c_int] * 7 +
+                                 [_P, c_size_t, _P, c_int, _P, c_int, _P, _P, _P, _P, c_int, _P, _P, c_size_t, _P]),
     "dba_ba_cost_scratch_bytes": (c_size_t, [c_int] * 3),
     "dba_ba_cost": (c_int, [_P] * 7 + [c_int] * 4 + [_P, c_int, _P, c_size_t, _P]),
     "dba_corr_index_forward": (c_int, [_P, _P, _P] + [c_int] * 7 + [_P]),

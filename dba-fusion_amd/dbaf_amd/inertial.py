@@ -20,8 +20,22 @@ BACore.hessian_gtsam deliver the visual system in.  With db = b_i - bbar the res
 weighted by the inverse of the 9 x 9 preintegration covariance (order phi, v, p) and of the bias random walk's 6 x 6.
 The step solves H dx = v in the sign convention of BACore.hessian: the IMU right-hand side is -J^T L r.
 
-Not in scope: marginalisation (only diagonal priors exist), GNSS / odometer factors, step control across iterations (one
-damped Gauss-Newton step per call), visual-inertial initialisation.
+A sliding window (dbaf/depth_video.py:350-462: the temporary graph of what touches the departing keyframes, gtsam.marginalizeOut,
+the marginal factor carried into every later solve):
+
+    s = vio_window.split(video, ...)                       # s.marg: the arguments of the marginal BACore.init
+    marg_core.init(..., *s.marg ...); marg_core.hessian_gtsam(Tbc)
+    prior = win.marginalize(marg_core, pre, Tbc, m)        # Schur complement over the m oldest states: a DensePrior, no host read
+    win = win.slide(m, n_new)                              # the states that stay, new rows for the caller to fill
+    win.set_dense_prior(prior)                             # every later step() adds it, relinearised
+
+A DensePrior over the first K states holds a linearisation point x0 and (H [15K, 15K], b [15K]); its energy is
+delta^T H delta / 2 - b^T delta with delta = local(x0, x) = (Log(R0^T R), R0^T (p - p0), v - v0, bias - bias0) per state.  At the
+current states it adds H to the system's first 15K rows and columns and b - H delta to its right-hand side; the Jacobian of
+`local` is not applied (the relinearisation of a linear container factor, how the reference carries marg_factor).
+
+Not in scope: the bias covariance inflation at re-initialisation (depth_video.py:446-459), GNSS / odometer factors, step control
+across iterations (one damped Gauss-Newton step per call), visual-inertial initialisation.
 """
 import ctypes
 
@@ -127,6 +141,30 @@ def pack(preints, device="cuda"):
     return torch.from_numpy(np.ascontiguousarray(rows)).to(device)
 
 
+class DensePrior:
+    """A dense Gaussian prior over the first K states of the window it is set on (InertialWindow.set_dense_prior), float64 on
+    the device: the linearisation point R0 [K,3,3], p0 [K,3], vel0 [K,3], bias0 [K,6], H [15K,15K] (symmetric to the bit when
+    marginalize() made it) and b [15K].  `status` (int32 [1], device; None for a hand-made prior): 1 when the marginalisation
+    that made it could not factorise its M_mm -- H and b are NaN then."""
+
+    def __init__(self, R0, p0, vel0, bias0, H, b, status=None):
+        import torch
+        K = int(R0.shape[0])
+        shapes = ((R0, (K, 3, 3)), (p0, (K, 3)), (vel0, (K, 3)), (bias0, (K, 6)), (H, (15 * K, 15 * K)), (b, (15 * K,)))
+        for x, shape in shapes:
+            if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float64 and x.is_contiguous()
+                    and tuple(x.shape) == shape and x.device == R0.device):
+                raise ValueError("DensePrior: float64 contiguous device tensors R0 [K,3,3], p0 [K,3], vel0 [K,3], bias0 [K,6], "
+                                 "H [15K,15K], b [15K] on one device; got %s where %s was expected"
+                                 % (tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__, shape))
+        if K < 1:
+            raise ValueError("DensePrior: K >= 1")
+        self.K, self.R0, self.p0, self.vel0, self.bias0, self.H, self.b, self.status = K, R0, p0, vel0, bias0, H, b, status
+
+    def tensors(self):
+        return (self.R0, self.p0, self.vel0, self.bias0, self.H, self.b)
+
+
 def _check_P(P):
     if P < 2 or P > MAX_P:
         raise ValueError("InertialWindow: 2 <= P <= %d states (15 P <= 384 unknowns), got %d" % (MAX_P, P))
@@ -134,7 +172,8 @@ def _check_P(P):
 
 class InertialWindow:
     """The inertial states of a window of P keyframes, float64 on the device: R [P,3,3], p [P,3] (world <- body), vel [P,3],
-    bias [P,6] = (ba, bg), gravity, and optional diagonal priors (set_prior)."""
+    bias [P,6] = (ba, bg), gravity, optional diagonal priors (set_prior) and an optional dense prior over its first states
+    (set_dense_prior; marginalize() makes one)."""
 
     def __init__(self, P, device="cuda", gravity=GRAVITY):
         import torch
@@ -147,6 +186,7 @@ class InertialWindow:
         self.p, self.vel, self.bias = z(self.P, 3), z(self.P, 3), z(self.P, 6)
         self.gravity = tuple(float(x) for x in gravity)
         self.prior = None                    # (R, p, vel, bias, w): anchors and weights [P, 15]
+        self.dense = None                    # a DensePrior over the first dense.K states
         self.dx = z(self.P, 15)              # what the last step() solved for
         self.status = torch.zeros(1, dtype=torch.int32, device=self.device)   # 1: its system could not be factorised
         self._need = _lib.load().dba_inertial_scratch_bytes(self.P)
@@ -181,12 +221,28 @@ class InertialWindow:
     def clear_prior(self):
         self.prior = None
 
+    def set_dense_prior(self, prior):
+        """every later step() and marginalize() adds `prior` (a DensePrior over K <= P states), relinearised at the states
+        they find; the tensors are referenced, not copied"""
+        if not isinstance(prior, DensePrior):
+            raise TypeError("InertialWindow.set_dense_prior: a DensePrior, got %s" % type(prior).__name__)
+        if prior.K > self.P or prior.H.device != self.device:
+            raise ValueError("InertialWindow.set_dense_prior: a prior over %d states on %s, this window has %d on %s"
+                             % (prior.K, prior.H.device, self.P, self.device))
+        self.dense = prior
+
+    def clear_dense_prior(self):
+        self.dense = None
+
     def _state(self):
         from . import _lib
         s = _lib.InertialState()
         s.R, s.p, s.vel, s.bias = (x.data_ptr() for x in (self.R, self.p, self.vel, self.bias))
         if self.prior is not None:
             s.prior_R, s.prior_p, s.prior_vel, s.prior_bias, s.prior_w = (x.data_ptr() for x in self.prior)
+        if self.dense is not None:
+            s.dense_R, s.dense_p, s.dense_vel, s.dense_bias, s.dense_H, s.dense_b = (x.data_ptr() for x in self.dense.tensors())
+            s.dense_K = self.dense.K
         s.gravity[:] = self.gravity
         return s
 
@@ -219,22 +275,12 @@ class InertialWindow:
         (float64, device; rewritten by the next step).  A system that cannot be factorised gives NaN there, sets self.status
         and moves nothing.  Six launches on the current stream, no host synchronisation: recordable into a hipGraph once the
         edge set stands.  Tbc as for BACore.hessian_gtsam."""
-        from . import _lib, fusion
-        import droid_backends
+        from . import _lib
         preint = self._preint(preint)
         if bacore.P != self.P:
             raise RuntimeError("InertialWindow.step: the BA window has %d poses, this window %d states" % (bacore.P, self.P))
-        if bacore._linearised is None:
-            raise RuntimeError("InertialWindow.step: hessian() has not run")
-        if droid_backends._BACORE_OWNER.get(bacore.ws.data_ptr(), id(bacore)) != id(bacore):
-            raise RuntimeError("InertialWindow.step: another BACore of the same window shape has linearised into the shared "
-                               "workspace since this object's hessian(); call hessian() again first")
-        if bacore.poses.device != self.device:
-            raise RuntimeError("InertialWindow.step: the BA window lives on %s, this window on %s" % (bacore.poses.device, self.device))
-        # (a call stage 0 refused moves neither poses nor depths: the inertial states must not move alone)
-        droid_backends._raise_pending_eta_error((bacore.ws, bacore.nbytes), bacore._dims())
-        A = np.asarray(Tbc, np.float64) if (not hasattr(Tbc, "matrix") and np.shape(Tbc) == (6, 6)) else fusion.tangent_block(Tbc)
-        a36 = (ctypes.c_double * 36)(*np.ascontiguousarray(A).reshape(-1))
+        self._check_core(bacore, "step")
+        a36 = self._a36(Tbc)
         st = self._state()
         p = lambda x: ctypes.c_void_p(x.data_ptr())   # noqa: E731
         rc = _lib.load().dba_inertial_step(ctypes.byref(st), self.P, p(preint), int(preint.shape[0]), ctypes.cast(a36, ctypes.c_void_p),
@@ -243,3 +289,79 @@ class InertialWindow:
                                            p(bacore.ws), bacore.nbytes, _lib.stream(self.device))
         _lib.check(rc, "dba_inertial_step")
         return self.dx
+
+    def _check_core(self, bacore, op):
+        """what step() and marginalize() ask of a BACore: linearised, by this object, on this device, stage 0 not refused"""
+        import droid_backends
+        if bacore._linearised is None:
+            raise RuntimeError("InertialWindow.%s: hessian() has not run" % op)
+        if droid_backends._BACORE_OWNER.get(bacore.ws.data_ptr(), id(bacore)) != id(bacore):
+            raise RuntimeError("InertialWindow.%s: another BACore of the same window shape has linearised into the shared "
+                               "workspace since this object's hessian(); call hessian() again first" % op)
+        if bacore.poses.device != self.device:
+            raise RuntimeError("InertialWindow.%s: the BA window lives on %s, this window on %s" % (op, bacore.poses.device, self.device))
+        # (a call stage 0 refused moves neither poses nor depths: the inertial states must not move alone)
+        droid_backends._raise_pending_eta_error((bacore.ws, bacore.nbytes), bacore._dims())
+
+    @staticmethod
+    def _a36(Tbc):
+        from . import fusion
+        A = np.asarray(Tbc, np.float64) if (not hasattr(Tbc, "matrix") and np.shape(Tbc) == (6, 6)) else fusion.tangent_block(Tbc)
+        return (ctypes.c_double * 36)(*np.ascontiguousarray(A).reshape(-1))
+
+    def marginalize(self, bacore_marg, preint, Tbc, m, stabilizer=0.00025):
+        """The Schur complement over the m oldest states (1 <= m < P), at the current states: what gtsam.marginalizeOut returns
+        at dbaf/depth_video.py:357-443.  bacore_marg: a BACore initialised from vio_window's Split.marg on which hessian*() has
+        run -- Pm <= P poses wide, its pose 0 is state 0 -- or None when nothing was selected.  The system over
+        S = max(Pm, m + 1, K_old) states takes the marginal visual system (stabiliser and Tbc as in step()), the intervals
+        k -> k + 1 for k < m, the diagonal priors of the states < m and the whole dense prior of this window (K_old states),
+        relinearised; no damping.  Returns a NEW DensePrior over the K = S - m states m .. S - 1, linearised where they stand;
+        this window's own prior and states are not written.  A M_mm that cannot be factorised gives NaN in H and b and 1 in the
+        result's `status`.  Five launches on the current stream, no host synchronisation."""
+        import torch
+        from . import _lib
+        preint = self._preint(preint)
+        m = int(m)
+        if not 1 <= m < self.P:
+            raise ValueError("InertialWindow.marginalize: 1 <= m < P = %d, got %d" % (self.P, m))
+        Pm, dims, ws, nbytes = 0, (0, 0, 0, 0, 0, 0), None, 0
+        if bacore_marg is not None:
+            if bacore_marg.P > self.P:
+                raise RuntimeError("InertialWindow.marginalize: the marginal BA window has %d poses, this window %d states"
+                                   % (bacore_marg.P, self.P))
+            self._check_core(bacore_marg, "marginalize")
+            Pm, dims, ws, nbytes = bacore_marg.P, bacore_marg._dims(), ctypes.c_void_p(bacore_marg.ws.data_ptr()), bacore_marg.nbytes
+        Kn = max(Pm, m + 1, self.dense.K if self.dense is not None else 0) - m
+        with torch.cuda.device(self.device):
+            e = lambda *s: torch.empty(*s, dtype=torch.float64, device=self.device)   # noqa: E731
+            out = DensePrior(e(Kn, 3, 3), e(Kn, 3), e(Kn, 3), e(Kn, 6), e(15 * Kn, 15 * Kn), e(15 * Kn),
+                             torch.empty(1, dtype=torch.int32, device=self.device))
+        st = self._state()
+        p = lambda x: ctypes.c_void_p(x.data_ptr())   # noqa: E731
+        rc = _lib.load().dba_inertial_marginalize(ctypes.byref(st), self.P, p(preint), int(preint.shape[0]),
+                                                  ctypes.cast(self._a36(Tbc), ctypes.c_void_p), float(stabilizer), m, *dims, ws, nbytes,
+                                                  p(out.H), 15 * Kn, p(out.b), 15 * Kn, p(out.R0), p(out.p0), p(out.vel0), p(out.bias0), Kn,
+                                                  p(out.status), p(self._scratch), self._need, _lib.stream(self.device))
+        _lib.check(rc, "dba_inertial_marginalize")
+        return out
+
+    def slide(self, m, n_new=0):
+        """A new window of P - m + n_new states: the states m .. P - 1 (device row copies), then n_new copies of the last state
+        for the caller to overwrite from the video or from IMU prediction.  Diagonal priors move with their states (new rows
+        carry none).  The dense prior is NOT carried: the caller sets the one marginalize() returned."""
+        import torch
+        m, n_new = int(m), int(n_new)
+        if not 1 <= m < self.P or n_new < 0:
+            raise ValueError("InertialWindow.slide: 1 <= m < P = %d and n_new >= 0, got m = %d, n_new = %d" % (self.P, m, n_new))
+        keep = self.P - m
+        win = InertialWindow(keep + n_new, self.device, self.gravity)
+
+        def rows(src):
+            return torch.cat([src[m:], src[-1:].expand(n_new, *src.shape[1:])]).contiguous()
+
+        for name in ("R", "p", "vel", "bias"):
+            getattr(win, name).copy_(rows(getattr(self, name)))
+        if self.prior is not None:
+            w = torch.cat([self.prior[4][m:], torch.zeros(n_new, 15, dtype=torch.float64, device=self.device)]).contiguous()
+            win.prior = tuple(rows(x) for x in self.prior[:4]) + (w,)
+        return win

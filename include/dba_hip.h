@@ -448,6 +448,14 @@ typedef struct {
   double *R, *p, *vel, *bias;
   const double *prior_R, *prior_p, *prior_vel, *prior_bias, *prior_w;
   double gravity[3];
+  /* The dense prior over the first dense_K states (1 <= dense_K <= P), float64 on the device; all six NULL and dense_K = 0:
+   * none.  Linearisation point dense_R [K, 3, 3], dense_p [K, 3], dense_vel [K, 3], dense_bias [K, 6]; dense_H [15 K, 15 K]
+   * (symmetric), dense_b [15 K].  Its energy is delta^T H delta / 2 - b^T delta with, per state,
+   *     delta = (Log(R0^T R), R0^T (p - p0), vel - vel0, bias - bias0);
+   * it adds H to the first 15 K rows and columns of the step's system and b - H delta to its right-hand side (the Jacobian of
+   * delta is not applied: the relinearisation of a linear container factor). */
+  const double *dense_R, *dense_p, *dense_vel, *dense_bias, *dense_H, *dense_b;
+  int dense_K;
 } dba_inertial_state;
 
 /* bytes of the scratch both entries below work in for P states; 0 for a P they refuse */
@@ -479,6 +487,33 @@ int dba_inertial_step(const dba_inertial_state *st, int P, const double *preint,
                       double stabilizer, float lm, float ep, float *poses, float *disps, const int64_t *ii, const int64_t *jj, int N,
                       int B, int ht, int wd, int t0, int t1, double *dx_out, int *status_out, void *scratch, size_t scratch_bytes,
                       void *ws, size_t ws_bytes, dba_stream_t stream);
+
+/* bytes of the scratch dba_inertial_marginalize works in for a window of P states (what dba_inertial_scratch_bytes(P) returns:
+ * one scratch serves both entries); 0 for a P they refuse */
+size_t dba_inertial_marg_scratch_bytes(int P);
+
+/* Marginalise the m oldest of the P states into a dense prior over the states that stay coupled to them (the reference's
+ * gtsam.marginalizeOut, dbaf/depth_video.py:357-443), at the current states, on the device.  The system over
+ * S = max(Pm, m + 1, dense_K) states takes, per entry and in this order: the reduced camera system of the MARGINAL BA window in
+ * `ws` (Pm = t1 - t0 poses, its pose 0 is state 0; `stabilizer` and A36 as dba_inertial_step applies them; ws NULL: Pm = 0 and
+ * N .. t1 are not read), the intervals k -> k + 1 for k < m, the diagonal priors of the states < m, and the whole dense prior
+ * of `st`, relinearised.  No damping.  With mm = the first 15 m unknowns and kk = the other 15 (S - m):
+ *     H_new = M_kk - M_km M_mm^-1 M_mk,   b_new = rhs_k - M_km M_mm^-1 rhs_m,
+ * the linearisation point = the states m .. S - 1.  K_new = S - m.
+ *   H_new [h_rows >= 15 K_new rows of its own length]: written dense, [15 K_new, 15 K_new] row-major, symmetric to the bit;
+ *   b_new [b_rows >= 15 K_new]; R0 [x0_rows, 3, 3], p0 [x0_rows, 3], vel0 [x0_rows, 3], bias0 [x0_rows, 6], x0_rows >= K_new.
+ *   None of them may be memory of the dense prior in `st`, which is only read.
+ *   status_out (device int, may be NULL): 1 when M_mm had a pivot that was not positive -- then H_new and b_new are NaN and
+ *   nothing else is written -- else 0.
+ * Five launches (the linearisation, the assembly in three dense parts, the factor of M_mm, one forward substitution per column
+ * over as many workgroups, the Schur products), all float64, no atomics, no host synchronisation, bit-identical from run to run.
+ * Refused BEFORE ANY RUNTIME CALL: what dba_inertial_linearize refuses (a dense prior given in part or with dense_K outside
+ * [1, P] among it), a null or misaligned A36 or output, m < 1, m >= P, Pm > P, a capacity below K_new, sizes ba_plan refuses
+ * (DBA_ERR_ARG); P > DBA_INERTIAL_MAX_P (DBA_ERR_UNSUPPORTED); a short scratch or BA workspace (DBA_ERR_WORKSPACE). */
+int dba_inertial_marginalize(const dba_inertial_state *st, int P, const double *preint, int preint_rows, const double *A36,
+                             double stabilizer, int m, int N, int B, int ht, int wd, int t0, int t1, void *ws, size_t ws_bytes,
+                             double *H_new, int h_rows, double *b_new, int b_rows, double *R0, double *p0, double *vel0,
+                             double *bias0, int x0_rows, int *status_out, void *scratch, size_t scratch_bytes, dba_stream_t stream);
 
 /* The BA cost report (csrc/ba_cost.hip): what the linearisation minimises, per edge.  For edge n with i = ii[n], j = jj[n] and
  * pixel k = v * wd + u: Gij = Tj Ti^-1 (i == j: the fixed stereo baseline t = (-0.1, 0, 0), q = identity) formed in float64
